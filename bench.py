@@ -4,6 +4,12 @@ on synthetic weights, N GPUs of one node (one process per GPU, pixels dealt in 8
 all_gather per frame).  Prints ONE JSON line on rank 0 (see the contract in the task statement).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size 512] [--mode relight|sphere_tracing|anisdf|novel_light]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, soaks and warms up, times the K steps and prints the line (rays/s, ms_per_step, the roofline of the timed
+steps).  `--full` adds the legs that take runs of their own: the CPU baseline and the PSNR against the oracle on its sample, the
+strictly sequential frames (`ms_per_step_sequential`) and, with `--animate`, the same frames posed before the loop.
+`--dump-outputs DIR` writes what the last timed step returned (DIR/<name>.npy, float32) for output-by-output comparisons of builds.
 
 `--gpus N` with N > 1 outside a torchrun environment makes this process a LAUNCHER: it never touches the GPU, starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child (env:// rendezvous on 127.0.0.1, like the
@@ -166,6 +172,31 @@ def hbm_traffic_per_launch(kernel, workload='relight512'):
     return None, None
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, value, name):
+    """--dump-outputs: the maps the last timed step returned (a tensor, or a dict of maps [1, rays, C] / [1, rays]) as path/<name>.npy in
+    float32.  Beyond DUMP_BYTES in all, every map keeps the same seeded sample of its rays (axis 1), listed in path/sample_rays.npy."""
+    import numpy as np
+    items = [(name, value)] if isinstance(value, torch.Tensor) else [(k, v) for k, v in value.items() if isinstance(v, torch.Tensor)]
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in items}
+    if not arrays:
+        raise SystemExit('bench.py --dump-outputs: the timed step returned no arrays')
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        n = {a.shape[1] for a in arrays.values() if a.ndim >= 2}
+        if len(n) != 1:
+            raise SystemExit(f'bench.py --dump-outputs: {total} bytes of maps without one common ray axis: {[a.shape for a in arrays.values()]}')
+        n = n.pop()
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * DUMP_BYTES / total)), replace=False))
+        arrays = {k: a[:, keep] for k, a in arrays.items()}
+        np.save(os.path.join(path, 'sample_rays.npy'), keep.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f'{k}.npy'), np.ascontiguousarray(a))
+
+
 def launch_ranks(args, argv):
     """parent of an N-rank job: has not initialised the GPU and never does (no exec of a GPU-initialised process either)."""
     with socket.socket() as so:
@@ -290,6 +321,8 @@ def main():
     ap.add_argument('--mode', default='relight', choices=['relight', 'sphere_tracing', 'anisdf', 'novel_light'])
     ap.add_argument('--probes', type=int, default=8, help='novel_light: number of 16x32 probes re-shaded per frame')
     ap.add_argument('--dtype', default='f16', choices=['f16', 'bf16'])
+    ap.add_argument('--full', action='store_true', help='also run the legs beside the headline figure: CPU baseline + PSNR vs the oracle, the strictly sequential frames, the pre-posed comparison of --animate')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='rank 0 writes the maps the last timed step returned to DIR/<name>.npy (float32; at most 64 MB in all, a seeded sample of rays beyond that)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--ground', action='store_true', help='relight: add the ground-plane pass (cfg.vis_ground_shading, SURVEY.md 8f row N1)')
     ap.add_argument('--emulate-world', type=int, default=0, help='tuning aid: render only rank 0\'s shard of an N-rank job on one GPU (no collective); value is then NOT a whole-job rate')
@@ -304,7 +337,7 @@ def main():
     ap.add_argument('--frames-in-flight', type=int, default=3, help='frames kept in flight on as many HIP streams (relightableavatar_amd/pipeline.py): the latency-bound small-kernel phase of frame f + 1 runs beside the light-visibility stage of frame f, the stages themselves are serialised by a gate.  1 = strictly sequential frames')
     ap.add_argument('--animate', action='store_true', help='every step renders a DIFFERENT frame of an animation: bone poses -> body state on the device (N3, ra_pose_frame) -> rays + box culling on the device (N2, ra_gen_rays) -> set_frame -> render, all inside the timed region and all asynchronous (the rays of a frame are generated one pipeline turn ahead; their count is read back behind an event)')
     ap.add_argument('--coverage', type=float, default=0.0, help='fraction of the frame the body covers: moves the camera in (0 = SURVEY.md 8d camera at 2 m, ~8 %% hit pixels; 0.35 = a frame-filling subject, camera at 0.96 m)')
-    ap.add_argument('--no-sequential', action='store_true', help='skip the strictly sequential leg (ms_per_step_sequential: one frame at a time, host sync after each, as the reference loop run.py:43-49)')
+    ap.add_argument('--no-sequential', action='store_true', help='with --full: skip the strictly sequential leg (ms_per_step_sequential: one frame at a time, host sync after each, as the reference loop run.py:43-49)')
     ap.add_argument('--trace-precision', type=int, default=1, choices=[0, 1, 2], help='cfg.trace_precision: 1 = the surface trace in compensated arithmetic (default), 0 = plain 16-bit operands everywhere (round 3), 2 = compensated everywhere')
     ap.add_argument('--body', default='blob', choices=['blob', 'split'], help='split: the hard-case body of tests/golden/switches.npz `split_body` (synthetic.SPLIT_BODY_KW: a horn pulled 0.57 m out of the body, shadowing it at distance) under the front key light, 12 shadow iterations unless --shadow-iters says otherwise')
     ap.add_argument('--weights', default='init', choices=['init', 'sharp'], help='sharp: trained-like synthetic weights (synthetic.SHARP_BANDS: live high-frequency encoding columns, cm-scale surface detail)')
@@ -312,6 +345,8 @@ def main():
     ap.add_argument('--key-light-share', type=float, default=-1.0, help='cfg.key_light_share (default: the configuration default 0.0078; 0 = no key-light tier: every shadow ray on plain f16 operands, round 5)')
     ap.add_argument('--skin-noise', type=float, default=2.0, help='synthetic body: per-vertex noise of the skinning logits (SURVEY.md 8d default 2.0; 0 = smooth, SMPL-like)')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('bench.py: --steps must be at least 1')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         launch_ranks(args, sys.argv[1:])
@@ -486,6 +521,8 @@ def main():
         if use_dist:
             dist.broadcast(ns, 0)
         n_soak = int(ns.item())
+        if anim is not None:      # the timed steps start at frame 0 of the pose cycle whatever the soak measured: the same inputs every run
+            n_soak += -(5 + n_soak + args.warmup) % n_anim
         for _ in range(n_soak):
             step()
         n_soak += 5
@@ -518,7 +555,10 @@ def main():
     # also a frame's first-to-last-launch latency.  Counters / kernel timers are off: the roofline figures are the timed region's.
     dt_seq = None
     cnt_snapshot = [dict(e.counters()) for e in engs]
-    if not args.no_sequential:
+    if args.dump_outputs and rank == 0:         # what the last timed step returned (after the snapshot: reading lazy maps launches work)
+        dump_outputs(args.dump_outputs, out.result(), 'rgb_probes' if args.mode == 'novel_light' else 'out')
+        torch.cuda.synchronize(dev)
+    if args.full and not args.no_sequential:
         n_seq = max(2, min(args.steps, 10))
         sync()
         t1 = time.perf_counter()
@@ -530,7 +570,7 @@ def main():
     dt_static = None
     if anim is not None:
         rays_per_frame_anim = anim.rays / max(args.steps, 1)
-    if anim is not None and nw == 1:          # the same frames through the same pipeline with N3 + N2 done BEFORE the loop: what posing / culling inside it costs
+    if args.full and anim is not None and nw == 1:          # the same frames through the same pipeline with N3 + N2 done BEFORE the loop: what posing / culling inside it costs
         sync()
         anim.cached = [loader.batch(issue(e0, f)) for f in range(n_anim)]
         sync()
@@ -641,7 +681,7 @@ def main():
             if dt_static is not None:
                 line['ms_per_step_frames_posed_before_the_loop'] = dt_static * 1e3          # the same frames, N3 + N2 outside the loop
                 line['animate_over_preposed'] = dt / args.steps / dt_static
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'], ref = cpu_baseline(cfg, H, args.skin_noise, cam_dist=cam_dist)
             if args.mode in ('relight', 'sphere_tracing', 'anisdf') and not args.ground and args.emulate_world <= 1:
                 try:

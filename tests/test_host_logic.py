@@ -217,6 +217,31 @@ def test_bench_launcher_starts_n_ranks():
     assert r.returncode != 0 and 'WORLD_SIZE' in (r.stdout + r.stderr)
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every map of the last step as float32 <name>.npy; past the byte budget all maps keep the same seeded
+    sample of rays (listed in sample_rays.npy), identical from run to run"""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    from relightableavatar_amd.base_utils import dotdict
+    g = torch.Generator().manual_seed(1)
+    maps = dotdict(rgb_map=torch.rand(1, 1000, 3, generator=g, dtype=torch.float16), acc_map=torch.rand(1, 1000, generator=g), note='not an array')
+    bench.dump_outputs(str(tmp_path / 'a'), maps, 'out')
+    assert sorted(os.listdir(tmp_path / 'a')) == ['acc_map.npy', 'rgb_map.npy']
+    rgb = np.load(tmp_path / 'a' / 'rgb_map.npy')
+    assert rgb.dtype == np.float32 and np.array_equal(rgb, maps.rgb_map.float().numpy())
+    bench.dump_outputs(str(tmp_path / 't'), maps.acc_map, 'rgb_probes')
+    assert np.array_equal(np.load(tmp_path / 't' / 'rgb_probes.npy'), maps.acc_map.numpy())
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4000)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), maps, 'out')
+    keep = np.load(tmp_path / 'b' / 'sample_rays.npy').astype(np.int64)
+    assert 0 < len(keep) < 1000 and np.array_equal(keep, np.load(tmp_path / 'c' / 'sample_rays.npy'))
+    got = {k: np.load(tmp_path / 'b' / f'{k}.npy') for k in ('rgb_map', 'acc_map')}
+    assert sum(a.nbytes for a in got.values()) <= 4000
+    assert np.array_equal(got['rgb_map'], rgb[:, keep]) and np.array_equal(got['acc_map'], maps.acc_map.numpy()[:, keep])
+
+
 @pytest.mark.parametrize('extra', [[], ['--ground', '--mode', 'novel_light', '--probes', '2']])
 def test_frames_in_flight_keep_their_collectives_apart_gloo_world4(extra):
     """Four ranks, THREE frames in flight in one process group (bench.py --dry --frames-in-flight 3: the gathers of frames f, f + 1, f + 2

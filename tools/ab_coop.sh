@@ -9,8 +9,8 @@ for coop in 0 8192; do
   echo "== RA_K3C_COOP_MAX=$coop: kernel time per launch (tools/bench_k3c.py)"
   RA_K3C_SIZES=300,1200,2400,4096,5000,8192 python tools/bench_k3c.py 2>&1 | grep "precision 2"
   echo "== RA_K3C_COOP_MAX=$coop: frames (bench.py; ms in flight, sequential)"
-  for r in 0 4; do python bench.py --emulate-world 8 --emulate-rank $r --no-cpu-baseline 2>/dev/null | p "relight 512 N=8 rank $r"; done
-  python bench.py --mode sphere_tracing --size 256 --no-cpu-baseline 2>/dev/null | p "sphere tracing 256"
-  python bench.py --mode sphere_tracing --emulate-world 8 --no-cpu-baseline 2>/dev/null | p "sphere tracing 512 N=8 rank 0"
-  python bench.py --mode novel_light --ground --emulate-world 8 --no-cpu-baseline 2>/dev/null | p "config 5 N=8 rank 0"
+  for r in 0 4; do python bench.py --full --emulate-world 8 --emulate-rank $r --no-cpu-baseline 2>/dev/null | p "relight 512 N=8 rank $r"; done
+  python bench.py --full --mode sphere_tracing --size 256 --no-cpu-baseline 2>/dev/null | p "sphere tracing 256"
+  python bench.py --full --mode sphere_tracing --emulate-world 8 --no-cpu-baseline 2>/dev/null | p "sphere tracing 512 N=8 rank 0"
+  python bench.py --full --mode novel_light --ground --emulate-world 8 --no-cpu-baseline 2>/dev/null | p "config 5 N=8 rank 0"
 done

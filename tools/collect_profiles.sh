@@ -12,35 +12,35 @@ OUT=$R/gpurun_out/prof
 RN=${RA_ROUND:-r06}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --steps 20 --warmup 3 > $OUT/${RN}_bench.json 2> $OUT/bench.err
+python3 $R/bench.py --full --steps 20 --warmup 3 > $OUT/${RN}_bench.json 2> $OUT/bench.err
 : > $OUT/${RN}_bench_other_shapes.jsonl
-python3 $R/bench.py --mode sphere_tracing --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_bench_other_shapes.jsonl 2>> $OUT/bench.err
-python3 $R/bench.py --mode anisdf --steps 10 --warmup 2 --no-cpu-baseline >> $OUT/${RN}_bench_other_shapes.jsonl 2>> $OUT/bench.err
-python3 $R/bench.py --ground --steps 5 --warmup 2 --no-cpu-baseline >> $OUT/${RN}_bench_other_shapes.jsonl 2>> $OUT/bench.err
-python3 $R/bench.py --mode novel_light --size 1024 --probes 8 --steps 5 --warmup 2 --no-cpu-baseline >> $OUT/${RN}_bench_other_shapes.jsonl 2>> $OUT/bench.err
-python3 $R/bench.py --skin-noise 0 --steps 20 --warmup 3 > $OUT/${RN}_bench_skin_noise0.json 2>> $OUT/bench.err        # the smooth body, with its PSNR
-python3 $R/bench.py --coverage 0.35 --steps 10 --warmup 2 > $OUT/${RN}_bench_coverage35.json 2>> $OUT/bench.err          # a frame-filling subject (camera at 0.96 m), with its PSNR
-python3 $R/bench.py --trace-precision 0 --steps 20 --warmup 3 > $OUT/${RN}_bench_trace_precision0.json 2>> $OUT/bench.err  # round 3's arithmetic (plain f16 surface trace): what the compensated tier costs and buys
-python3 $R/bench.py --trace-precision 2 --steps 10 --warmup 3 > $OUT/${RN}_bench_trace_precision2.json 2>> $OUT/bench.err  # every distance query compensated: the tier that meets max |err| <= 1e-2 on every pixel, and its price
-python3 $R/bench.py --body split --steps 10 --warmup 3 > $OUT/${RN}_bench_body_split.json 2>> $OUT/bench.err               # the hard-case body (a part that shadows the body at distance, front key light, 12 shadow iterations)
-python3 $R/bench.py --body split --weights sharp --steps 10 --warmup 3 > $OUT/${RN}_bench_body_split_weights_sharp.json 2>> $OUT/bench.err
-python3 $R/bench.py --weights sharp --steps 10 --warmup 3 > $OUT/${RN}_bench_weights_sharp.json 2>> $OUT/bench.err
+python3 $R/bench.py --full --mode sphere_tracing --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_bench_other_shapes.jsonl 2>> $OUT/bench.err
+python3 $R/bench.py --full --mode anisdf --steps 10 --warmup 2 --no-cpu-baseline >> $OUT/${RN}_bench_other_shapes.jsonl 2>> $OUT/bench.err
+python3 $R/bench.py --full --ground --steps 5 --warmup 2 --no-cpu-baseline >> $OUT/${RN}_bench_other_shapes.jsonl 2>> $OUT/bench.err
+python3 $R/bench.py --full --mode novel_light --size 1024 --probes 8 --steps 5 --warmup 2 --no-cpu-baseline >> $OUT/${RN}_bench_other_shapes.jsonl 2>> $OUT/bench.err
+python3 $R/bench.py --full --skin-noise 0 --steps 20 --warmup 3 > $OUT/${RN}_bench_skin_noise0.json 2>> $OUT/bench.err        # the smooth body, with its PSNR
+python3 $R/bench.py --full --coverage 0.35 --steps 10 --warmup 2 > $OUT/${RN}_bench_coverage35.json 2>> $OUT/bench.err          # a frame-filling subject (camera at 0.96 m), with its PSNR
+python3 $R/bench.py --full --trace-precision 0 --steps 20 --warmup 3 > $OUT/${RN}_bench_trace_precision0.json 2>> $OUT/bench.err  # round 3's arithmetic (plain f16 surface trace): what the compensated tier costs and buys
+python3 $R/bench.py --full --trace-precision 2 --steps 10 --warmup 3 > $OUT/${RN}_bench_trace_precision2.json 2>> $OUT/bench.err  # every distance query compensated: the tier that meets max |err| <= 1e-2 on every pixel, and its price
+python3 $R/bench.py --full --body split --steps 10 --warmup 3 > $OUT/${RN}_bench_body_split.json 2>> $OUT/bench.err               # the hard-case body (a part that shadows the body at distance, front key light, 12 shadow iterations)
+python3 $R/bench.py --full --body split --weights sharp --steps 10 --warmup 3 > $OUT/${RN}_bench_body_split_weights_sharp.json 2>> $OUT/bench.err
+python3 $R/bench.py --full --weights sharp --steps 10 --warmup 3 > $OUT/${RN}_bench_weights_sharp.json 2>> $OUT/bench.err
 : > $OUT/${RN}_bench_animate.jsonl
-python3 $R/bench.py --animate --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_bench_animate.jsonl 2>> $OUT/bench.err   # N3 + N2 inside the timed region
-python3 $R/bench.py --animate --frames-in-flight 1 --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_bench_animate.jsonl 2>> $OUT/bench.err
-python3 $R/bench.py --animate --mode sphere_tracing --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_bench_animate.jsonl 2>> $OUT/bench.err
+python3 $R/bench.py --full --animate --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_bench_animate.jsonl 2>> $OUT/bench.err   # N3 + N2 inside the timed region
+python3 $R/bench.py --full --animate --frames-in-flight 1 --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_bench_animate.jsonl 2>> $OUT/bench.err
+python3 $R/bench.py --full --animate --mode sphere_tracing --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_bench_animate.jsonl 2>> $OUT/bench.err
 # sequential frames (one in flight) next to the default two: the whole frame and one rank's share of 2 / 4 / 8
 : > $OUT/${RN}_frames_in_flight.jsonl
-for d in 1 2 3 4; do python3 $R/bench.py --frames-in-flight $d --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_frames_in_flight.jsonl 2>> $OUT/bench.err; done
-for d in 1 2; do for n in 2 4 8; do python3 $R/bench.py --frames-in-flight $d --emulate-world $n --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_frames_in_flight.jsonl 2>> $OUT/bench.err; done; done
-python3 $R/bench.py --frames-in-flight 1 --mode sphere_tracing --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_frames_in_flight.jsonl 2>> $OUT/bench.err
+for d in 1 2 3 4; do python3 $R/bench.py --full --frames-in-flight $d --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_frames_in_flight.jsonl 2>> $OUT/bench.err; done
+for d in 1 2; do for n in 2 4 8; do python3 $R/bench.py --full --frames-in-flight $d --emulate-world $n --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_frames_in_flight.jsonl 2>> $OUT/bench.err; done; done
+python3 $R/bench.py --full --frames-in-flight 1 --mode sphere_tracing --steps 20 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_frames_in_flight.jsonl 2>> $OUT/bench.err
 : > $OUT/${RN}_emulate_world.jsonl
 # EVERY rank's share (the slowest rank sets the frame time of a real job): config.emulate_rank says which
-for n in 2 4 8; do for r in $(seq 0 $((n-1))); do python3 $R/bench.py --emulate-world $n --emulate-rank $r --steps 20 --warmup 3 --soak 1 --no-cpu-baseline >> $OUT/${RN}_emulate_world.jsonl 2>> $OUT/bench.err; done; done
+for n in 2 4 8; do for r in $(seq 0 $((n-1))); do python3 $R/bench.py --full --emulate-world $n --emulate-rank $r --steps 20 --warmup 3 --soak 1 --no-cpu-baseline >> $OUT/${RN}_emulate_world.jsonl 2>> $OUT/bench.err; done; done
 # config 5 (1024 x 1024, 8 probes) and the README command (novel light + ground) as one rank of an N-rank job
 : > $OUT/${RN}_emulate_world_config5.jsonl
-for n in 1 2 4 8; do for r in $(seq 0 $((n-1))); do python3 $R/bench.py --emulate-world $n --emulate-rank $r --size 1024 --mode novel_light --probes 8 --steps 10 --warmup 3 --soak 1 --no-cpu-baseline >> $OUT/${RN}_emulate_world_config5.jsonl 2>> $OUT/bench.err; done; done
-for n in 1 2 4 8; do python3 $R/bench.py --emulate-world $n --size 512 --mode novel_light --ground --probes 2 --steps 10 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_emulate_world_config5.jsonl 2>> $OUT/bench.err; done
+for n in 1 2 4 8; do for r in $(seq 0 $((n-1))); do python3 $R/bench.py --full --emulate-world $n --emulate-rank $r --size 1024 --mode novel_light --probes 8 --steps 10 --warmup 3 --soak 1 --no-cpu-baseline >> $OUT/${RN}_emulate_world_config5.jsonl 2>> $OUT/bench.err; done; done
+for n in 1 2 4 8; do python3 $R/bench.py --full --emulate-world $n --size 512 --mode novel_light --ground --probes 2 --steps 10 --warmup 3 --no-cpu-baseline >> $OUT/${RN}_emulate_world_config5.jsonl 2>> $OUT/bench.err; done
 $R/tools/frame_anatomy.sh w8 44 -- --emulate-world 8 --steps 10 --warmup 3 > $OUT/${RN}_emulate_world8_kernels.txt 2>> $OUT/bench.err
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o r -- python3 $R/bench.py --steps 7 --warmup 2 --no-cpu-baseline --soak 0 > /dev/null 2>&1
