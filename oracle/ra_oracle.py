@@ -317,15 +317,85 @@ def geodesic_knn(pts, verts, norm, tverts, K, th, use_geodesic_filter=True):
 
 # ----------------------------------------------------------------------------- networks
 
+GRAD_SCALE = 16.0       # csrc/ra_k4.hpp: the backward pass carries every gradient times 2^4 (f16 headroom)
+
+
+class _KernelTransposedProduct(torch.autograd.Function):
+    """an emulated nn.Linear whose forward value `y` was computed elsewhere; backward = the K4 kernel's transposed product:
+    u = W^T q(delta * GRAD_SCALE) / GRAD_SCALE with the weights `wb` as the backward stream packs them, fp32 accumulate.
+    dt None: no rounding of delta (the SDF head's row 0 seeds the backward pass in fp32).  stats: largest |delta * GRAD_SCALE|
+    and how many nonzero deltas fall below the operand type's smallest normal value."""
+
+    @staticmethod
+    def forward(ctx, x, y, wb, dt, stats):
+        ctx.save_for_backward(wb)
+        ctx.dt, ctx.stats = dt, stats
+        return y.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        wb, = ctx.saved_tensors
+        if ctx.dt is not None:
+            gs = g * GRAD_SCALE
+            if ctx.stats is not None:
+                a = gs.abs()
+                nz = a > 0
+                ctx.stats['max_abs'] = max(ctx.stats.get('max_abs', 0.0), float(a.max()) if a.numel() else 0.0)
+                ctx.stats['n_nonzero'] = ctx.stats.get('n_nonzero', 0) + int(nz.sum())
+                ctx.stats['n_subnormal'] = ctx.stats.get('n_subnormal', 0) + int((nz & (a < torch.finfo(ctx.dt).tiny)).sum())
+            g = gs.to(ctx.dt).float() / GRAD_SCALE
+        return g @ wb, None, None, None, None
+
+
+class _TapedSoftplus(torch.autograd.Function):
+    """Softplus(beta=100) whose derivative is the K4 kernel's: sigma'(z) = 1 - 2^-y' from the activation the forward kernel
+    tapes, y' = y * SP_SCALE rounded to the operand type (EPI_GRAD_SP)"""
+
+    @staticmethod
+    def forward(ctx, z, dt):
+        y = softplus100(z)
+        ctx.save_for_backward((y * OracleNet.SP_SCALE).to(dt).float())
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        yq, = ctx.saved_tensors
+        return g * (1.0 - torch.exp2(-yq)), None
+
+
+class _SignMaskRelu(torch.autograd.Function):
+    """ReLU whose derivative is the K4 kernel's: the gradient passes where the pre-activation's sign bit is clear (EPI_GRAD_RELU)"""
+
+    @staticmethod
+    def forward(ctx, z):
+        ctx.save_for_backward(~torch.signbit(z))
+        return F.relu(z)
+
+    @staticmethod
+    def backward(ctx, g):
+        m, = ctx.saved_tensors
+        return g * m
+
+
 class OracleNet:
     """Plain-weight view of the reference state_dict + frame-independent ops."""
 
-    def __init__(self, sd: dict, cfg, emulate: Optional[str] = None, kernel_like: bool = False):
+    def __init__(self, sd: dict, cfg, emulate: Optional[str] = None, kernel_like: bool = False, emulate_backward: bool = False):
         """emulate: None (fp32, the reference's arithmetic) | 'f16' | 'bf16' — every nn.Linear of the MLPs rounds its input
         and its weight to that type and accumulates in fp32 (what a 16-bit-operand MFMA does; SURVEY.md:305 probe).  It is the
         floor any 16-bit-operand kernel can reach.  kernel_like additionally mirrors the HIP kernels' two deliberate
         deviations from a plain operand rounding: the pose condition enters through an fp32 per-frame bias (never rounded), and
-        the coordinate / frequency-0 encoding channels of the SDF net's two encoding-fed layers are carried as hi + lo pairs."""
+        the coordinate / frequency-0 encoding channels of the SDF net's two encoding-fed layers are carried as hi + lo pairs.
+        emulate_backward (with emulate 'f16' | 'bf16' and kernel_like): autograd through the geometry networks (d sdf / d bpts,
+        the normals) rounds the way the reverse-mode kernel K4 does (csrc/ra_k4.hpp, backward stream of csrc/ra_pack.cpp) and in
+        no other way: every transposed product takes q(delta * GRAD_SCALE) and the UNSCALED weights as packed (the SDF net's
+        1/sqrt(2) fold included, the hi + lo duplicates of the encoding columns not), fp32 accumulate; sigma' = 1 - 2^-q(y') from
+        the taped scaled activation; ReLU masks from the pre-activations' sign bits; the SDF head's row 0 seeds in fp32; the
+        residual net's seed resd_limit (1 - tanh^2) g is rounded like a delta; the encoding Jacobian and the final sums are fp32.
+        After each residual-net evaluation `relu_margin` holds per point the smallest |pre-activation| / rounding noise over the
+        2048 ReLU units (noise: u sqrt(sum (w x)^2) of the rounded operands, u the unit roundoff — the rms of the operand rounding's
+        error): where it is below ~1 a ReLU mask may differ between two arithmetics, and the gradient with it by a kink's height.
+        `delta_stats` collects the range of the rounded deltas."""
         self.cfg = cfg
         # 'f64acc': every nn.Linear is evaluated in float64 and rounded once to fp32 — a DIFFERENTLY ASSOCIATED (and more accurate)
         # fp32 arithmetic than the reference's BLAS sums: what it changes in a frame is what fp32 itself cannot pin (tools/precision_tiers.py).
@@ -340,6 +410,11 @@ class OracleNet:
         self.emulate = {None: None, 'f32': None, 'f64acc': None, 'f16': torch.float16, 'bf16': torch.bfloat16, 'f16x2': torch.float16,
                         'f16w2': torch.float16, 'f16a2': torch.float16}[emulate]
         self.kernel_like = bool(kernel_like) and self.emulate is not None
+        self.emulate_backward = bool(emulate_backward)
+        if self.emulate_backward and not (emulate in ('f16', 'bf16') and self.kernel_like):
+            raise ValueError("emulate_backward needs emulate='f16' | 'bf16' and kernel_like=True")
+        self.relu_margin = None
+        self.delta_stats = {}
         self.shadow_net = None           # tiered precision: another OracleNet (same weights) that answers the light-visibility queries
         f = lambda k: sd[k].detach().float().clone()
         self.resd = [(f(f'residual_deformation_network.mlp.linears.{i}.weight'),
@@ -372,7 +447,22 @@ class OracleNet:
 
     SP_SCALE = 144.26950408889634        # beta * log2(e): the kernels run the softplus layers in the domain y' = y * SP_SCALE
 
-    def lin(self, x, w, b, exact_cols=None, hilo_cols=None, scaled_x=False, scaled_w_cols=None):
+    def lin(self, x, w, b, exact_cols=None, hilo_cols=None, scaled_x=False, scaled_w_cols=None, seed=False):
+        """_lin below; with emulate_backward, autograd through it is the K4 kernel's transposed product (seed: the SDF head,
+        whose row 0 enters the backward pass in fp32)"""
+        if self.emulate_backward and torch.is_grad_enabled() and x.requires_grad:
+            with torch.no_grad():
+                y = self._lin(x.detach(), w, b, exact_cols, hilo_cols, scaled_x, scaled_w_cols)
+            return _KernelTransposedProduct.apply(x, y, w if seed else self._q(w), None if seed else self.emulate, self.delta_stats)
+        return self._lin(x, w, b, exact_cols, hilo_cols, scaled_x, scaled_w_cols)
+
+    def _relu(self, x):
+        return _SignMaskRelu.apply(x) if self.emulate_backward else F.relu(x)
+
+    def _softplus(self, x):
+        return _TapedSoftplus.apply(x, self.emulate) if self.emulate_backward else softplus100(x)
+
+    def _lin(self, x, w, b, exact_cols=None, hilo_cols=None, scaled_x=False, scaled_w_cols=None):
         """F.linear with the operand rounding of the emulation mode.  exact_cols: slice of input columns that stay fp32
         (the kernel folds them into a bias); hilo_cols: index list of input columns fed as hi + lo pairs against the same
         rounded weight (residual of the first rounding rounded again).  kernel_like only: scaled_x — the input is rounded as
@@ -431,13 +521,22 @@ class OracleNet:
         pe = positional_encoding(bpts, self.cfg.xyz_res)
         inp = torch.cat([pe, cond.expand(bpts.shape[0], -1)], dim=-1)
         x = inp
+        margin = None
         for i, (w, b) in enumerate(self.resd):
             if i == 4:
                 x = torch.cat([x, inp], dim=-1)
             c0 = (0 if i == 0 else 256) + pe.shape[-1]
+            xin = x
             x = self.lin(x, w, b, exact_cols=slice(c0, c0 + cond.shape[-1]) if i in (0, 4) else None)
             if i < 8:
-                x = F.relu(x)
+                if self.emulate_backward:
+                    with torch.no_grad():
+                        u = torch.finfo(self.emulate).eps / 2          # unit roundoff
+                        noise = u * (self._q(xin.detach()).square() @ self._q(w).square().T).sqrt()
+                        m = (x.detach().abs() / noise.clamp_min(1e-30)).amin(dim=-1)
+                        margin = m if margin is None else torch.minimum(margin, m)
+                x = self._relu(x)
+        self.relu_margin = margin
         return torch.tanh(x) * self.cfg.resd_limit
 
     def sdf_feat(self, cpts):
@@ -456,9 +555,9 @@ class OracleNet:
             elif l == 0:
                 hilo = list(range(9))            # x, sin(x), cos(x)
             pe_cols = slice(x.shape[-1] - inp.shape[-1], x.shape[-1]) if l in (0, 4) else None
-            x = self.lin(x, w, b, hilo_cols=hilo, scaled_x=l > 0, scaled_w_cols=pe_cols)
+            x = self.lin(x, w, b, hilo_cols=hilo, scaled_x=l > 0, scaled_w_cols=pe_cols, seed=l == 8)
             if l < 8:
-                x = softplus100(x)
+                x = self._softplus(x)
         return x[..., :1], x[..., 1:]
 
     def color_net(self, view, grad, feat, cond):
@@ -588,24 +687,31 @@ def bigpose_transform(net: OracleNet, x, fr, backward=False, invert=False):
     return affine_inverse(w2b) if invert else w2b
 
 
+def bigpose_query(net: OracleNet, bpts, cond):
+    """the geometry networks on big-pose points (inside forward_geometry, base_network.py:456-494; take_gradient net_utils.py:1215-1239):
+    bpts, resd, cpts, sdf, feat and ograd = d sdf / d bpts (un-normalised; the HIP debug_full hook's `grad`), all detached"""
+    bpts = bpts.detach().requires_grad_(True)
+    with torch.enable_grad():
+        resd = net.residuals(bpts, cond)
+        cpts = bpts + resd
+        sdf, feat = net.sdf_feat(cpts)
+        ograd = torch.autograd.grad(sdf, bpts, torch.ones_like(sdf))[0]
+    return bpts.detach(), resd.detach(), cpts.detach(), sdf.detach(), feat.detach(), ograd.detach()
+
+
 def forward_geometry(net: OracleNet, x, v, fr, dist_th=None):
     """Network.forward_geometry base_network.py:456-494 (eval). Normals via autograd (net_utils.py:1215-1239)."""
     dist_th = net.cfg.dist_th if dist_th is None else dist_th
     out = world_to_bigpose(net, x, fr, dist_th, v)
-    bpts = out.bpts.detach().requires_grad_(True)
-    with torch.enable_grad():
-        resd = net.residuals(bpts, fr.cond)
-        cpts = bpts + resd
-        sdf, feat = net.sdf_feat(cpts)
-        occ = sdf_to_occ(sdf, net.beta)
-        ograd = torch.autograd.grad(sdf, bpts, torch.ones_like(sdf))[0]
+    bpts, resd, cpts, sdf, feat, ograd = bigpose_query(net, out.bpts, fr.cond)
+    occ = sdf_to_occ(sdf, net.beta)
     norm = normalize(ograd)
     norm = torch.sum(out.big_A_bw[:, :3, :3].mT * norm[:, None, :], dim=-1)   # pose_dirs_to_tpose_dirs(big)
     norm = torch.sum(out.R_inv.mT * norm[:, None, :], dim=-1)                 # tpose_dirs_to_pose_dirs(A)
     norm = norm @ fr.R.mT                                                     # pose_dirs_to_world_dirs
     norm = normalize(norm)
-    out.bpts, out.cpts, out.resd = bpts.detach(), cpts.detach(), resd.detach()
-    out.sdf, out.occ, out.feat, out.norm, out.ograd = sdf.detach(), occ.detach(), feat.detach(), norm.detach(), ograd.detach()
+    out.bpts, out.cpts, out.resd = bpts, cpts, resd
+    out.sdf, out.occ, out.feat, out.norm, out.ograd = sdf, occ, feat, norm, ograd
     return out
 
 

@@ -6,6 +6,13 @@ Tolerances (f16 MFMA operands, fp32 accumulate; everything outside the MLPs is f
   resd, sdf, feat (MLP outputs) ...... 3e-4 abs (sdf), 2e-4 (feat); measured mean 4.5e-5 / 1.6e-5
   HDQ sdf ............................ 3e-4 abs
   normals (reverse-mode, K4 backward) .. 8e-3 abs per component, mean < 6e-4
+  rounding parity (rounding_parity) .... every fused-MLP kernel against the oracle's kernel-like emulation of ITS operand type, forward
+      and reverse mode (OracleNet emulate_backward: rounded deltas times GRAD_SCALE, packed transposed weights, sigma' from the tape,
+      sign-bit ReLU masks), f16 and bf16, init and trained-like weights: K3 at 2 / 4 / 8 waves, K4's gradient / sdf / features
+      (debug_full) and normal / material / rgb / occ (eng.forward).  floor = rms(emulation - f64acc); HIP must be as close to f64acc
+      as the emulation (total <= 1.1-1.25 x floor) and closer to the emulation than the floor (gap: grad <= 0.5, normal <= 0.6 x floor;
+      measured 0.20-0.40 / 0.27-0.51), plus p99.9 and max bounds; the bounds per quantity and why: PARITY below,
+      profiles/r07_rounding_parity.txt.  Weights truncated towards zero (one SDF-net layer) fail it, in K3 and K4, both types.
   albedo / roughness / occ ........... 1e-4 abs
   traced surfaces .................... median |st err| < 2e-4; rays whose 16-iteration trace has not converged
                                        amplify sdf noise (occ = 500 d / t), so frame maps are judged by the
@@ -38,7 +45,8 @@ Tolerances (f16 MFMA operands, fp32 accumulate; everything outside the MLPs is f
   stage bisect ....................... test_mlp_stage_matches_the_operand_rounding_emulation: HIP sdf vs the kernel-like
         emulation is several times closer than the emulation is to fp32, i.e. the in-kernel loss IS the operand rounding
         (v_sin/v_cos encodings, scaled-domain softplus through v_exp/v_log and the f16 re-pack add nothing measurable).
-bf16 operands are available (cfg.mlp_dtype='bf16'); they are ~10x noisier (sdf mean err 5e-4) and tested loosely.
+bf16 operands are available (cfg.mlp_dtype='bf16'); they are ~10x noisier (sdf mean err 5e-4).  They are held to the same rounding-parity
+criterion as f16 against their own emulation, and to the f16 path's bit-identity across launch geometries and K4 sub-batches.
 """
 import json
 import os
@@ -1547,6 +1555,18 @@ def test_streamed_k3_tile_boundaries(relight):
     (the stage hook: same networks, its own launch geometry), for fine counts around every tile boundary (ragged last tiles, a single
     point, an empty set)"""
     _, _, dev, body, eng = relight
+    _k3_tile_boundaries(eng, body, dev, 6e-4, 6e-5)
+
+
+def test_streamed_k3_tile_boundaries_bf16():
+    """the same with bf16 operands (ra_k3_bf16.hip: the bf16 instantiations of all three widths, the trimmed 8-wave stream and the
+    pair-ordered narrow stream): bit-identical across launch geometries, K3 within bf16 rounding of the full query's forward kernel"""
+    cfg, net, dev = build('relight', dtype='bf16')
+    body = synthetic.to_device(synthetic.make_body(0, posed=True), dev)
+    _k3_tile_boundaries(net.set_frame(body), body, dev, 5e-3, 5e-4)
+
+
+def _k3_tile_boundaries(eng, body, dev, tol_max, tol_mean):
     g = torch.Generator().manual_seed(21)
     vid = torch.randint(0, 6890, (70000,), generator=g)
     wv = (body.pverts[0] @ body.R[0].T + body.Th[0])[vid.to(dev)]
@@ -1558,7 +1578,7 @@ def test_streamed_k3_tile_boundaries(relight):
         sdf3 = eng.hdq_sdf(x, 0.125, False)                      # production path: coarse level + streamed K3, no blend
         _, sdf1, _ = eng.debug_mlp(o.bpts)                       # the full query's forward kernel on the same big-pose points
         e = (sdf3 - sdf1).abs()
-        assert torch.isfinite(sdf3).all() and float(e.max()) < 6e-4 and float(e.mean()) < 6e-5, (n, float(e.max()), float(e.mean()))
+        assert torch.isfinite(sdf3).all() and float(e.max()) < tol_max and float(e.mean()) < tol_mean, (n, float(e.max()), float(e.mean()))
     assert eng.hdq_sdf(x_all[:0], 0.125, True).numel() == 0
     # the three launch geometries (2 / 4 / 8 waves; the narrow ones run two row blocks at a time on a pair-ordered weight stream)
     # sum every accumulator's k-steps in the same order: a point's distance does not depend on the launch it is in, bit for bit
@@ -1581,8 +1601,18 @@ def test_full_query_tile_boundaries(mode):
     tiles) for counts around every tile / wave boundary, both head variants (material heads, colour net): a point's raw channels
     — normals included — must not depend on the batch it is evaluated in, bit for bit (ragged last tile, dead waves, a single
     point, an empty set), and must agree with the oracle"""
+    _full_query_tile_boundaries(mode, 'f16', 1.5e-2, 1e-3, 2e-3)
+
+
+@pytest.mark.parametrize('mode', ['relight', 'anisdf'])
+def test_full_query_tile_boundaries_bf16(mode):
+    """the same with bf16 operands (ra_k4_fwd_bf16.hip / ra_k4_bwd_bf16.hip); the fp32 oracle bounds are bf16's rounding level"""
+    _full_query_tile_boundaries(mode, 'bf16', 8e-2, 3e-3, 1e-3)         # measured 6.1e-2, 1.9e-3, 4.0e-4
+
+
+def _full_query_tile_boundaries(mode, dtype, tol_nrm_max, tol_nrm_mean, tol_other):
     from oracle import ra_oracle as O
-    cfg, net, dev = build(mode)
+    cfg, net, dev = build(mode, dtype=dtype)
     body = synthetic.to_device(synthetic.make_body(0, posed=True), dev)
     eng = net.set_frame(body)
     g = torch.Generator().manual_seed(33)
@@ -1608,8 +1638,9 @@ def test_full_query_tile_boundaries(mode):
     e = err(whole[:n], ref)
     ncol = slice(13, 16) if mode == 'relight' else slice(9, 12)
     other = [c for c in range(whole.shape[1]) if not (ncol.start <= c < ncol.stop)]
-    assert float(e[:, ncol].max()) < 1.5e-2 and float(e[:, ncol].mean()) < 1e-3, (float(e[:, ncol].max()), float(e[:, ncol].mean()))
-    assert float(e[:, other].max()) < 2e-3, float(e[:, other].max())
+    print(f'{mode} {dtype}: normals vs the fp32 oracle max {float(e[:, ncol].max()):.2e} mean {float(e[:, ncol].mean()):.2e}, other channels max {float(e[:, other].max()):.2e}')
+    assert float(e[:, ncol].max()) < tol_nrm_max and float(e[:, ncol].mean()) < tol_nrm_mean, (float(e[:, ncol].max()), float(e[:, ncol].mean()))
+    assert float(e[:, other].max()) < tol_other, float(e[:, other].max())
 
 
 def test_pose_frame_on_device(golden, relight):
@@ -2076,3 +2107,282 @@ def test_config5_key_light_tier_at_full_size():
     assert sum(over['shipped'].values()) < sum(over['round5'].values())
     assert all(v <= 4e-4 * nh for v in over['shipped'].values()) and all(v <= 7e-4 * nh for v in over['round5'].values())      # measured: <= 17 / <= 35 of 71 492
     assert comp['shipped'] < 0.16, comp            # 2 % (the surface trace) + the key lights' rays (48 lights at most)
+
+
+# ---- rounding parity: the fused-MLP kernels against the oracle's operand-rounding emulation (forward AND reverse mode), both operand types,
+# init and trained-like weights.  floor = rms(emulation - f64acc) is what rounding the MFMA operands costs; the kernel must be as close to
+# the float64-accumulated oracle as the emulation is (total) and much closer to the emulation than the emulation is to float64 (gap).
+# The oracle's emulate_backward mode mirrors K4's reverse pass (rounded deltas times GRAD_SCALE, unscaled packed transposed weights,
+# sigma' from the taped activation, sign-bit ReLU masks), so the gradient is held to the same criterion as the distance.
+# Bounds per quantity, as ratios to the floor: (total rms, gap rms, gap p99.9 / floor p99.9, gap max over ReLU-stable points / floor max).
+# Measured on 20 000 big-pose points (debug_full, K3) and 4 000 world points (eng.forward), worst case over f16 / bf16 x init / sharp
+# (profiles/r07_rounding_parity.txt):
+#   grad (d sdf / d bpts), normal: gap 0.20-0.40 / 0.27-0.51 — the reverse pass loses nothing beyond the emulated rounding of its deltas.
+#   sdf, feat, occ: gap up to 0.65 / 0.83 / 0.80 in f16, 0.24-0.39 in bf16.  What separates HIP from the emulation there is roundings
+#     flipped by fp32-level differences (the encodings' revolution-domain arguments, v_exp / v_log softplus, summation order): it costs
+#     2-3 x more of the floor in f16 than in bf16, as flips of 8 x finer roundings must; feat is compared after its final rounding
+#     (what the heads read), where one flip is a whole ulp.
+#   albedo / roughness: gap ~ floor — the emulation rounds the material heads in the unscaled domain, K4 runs them in the scaled
+#     softplus domain (weights rounded as w * SP_SCALE): held to the floor's total only.
+PARITY = {'grad': (1.1, 0.5, 0.6, 0.9), 'normal': (1.1, 0.6, 0.75, 0.85), 'sdf': (1.1, 0.75, 1.0, 1.3), 'feat': (1.1, 0.9, 1.1, 1.0),
+          'occ': (1.1, 0.9, 1.1, 1.2), 'rgb': (1.1, 0.7, 0.8, 1.0), 'albedo+rough': (1.25, 1.1, 1.25, 1.25)}
+STABLE_MARGIN = 0.25      # residual-net pre-activations this many rounding-noise units from zero (OracleNet.relu_margin) or more: ReLU-stable
+
+
+def _rms(a):
+    return float(a.pow(2).mean().sqrt())
+
+
+def rounding_parity(label, quantity, hip, emu, f64, stable=None):
+    """the pass criterion of the rounding-parity tests (bounds PARITY[quantity]): returns (figures, list of failed conditions); prints
+    one table row.  hip, emu, f64: (N, C) or (N,) values of the same N points; stable: bool (N,), the points whose residual-net ReLU
+    masks the rounding does not come near flipping (OracleNet.relu_margin), over which the per-point max is bounded"""
+    k_total, k_gap, k_p999, k_max = PARITY[quantity]
+    hip, emu, f64 = (torch.as_tensor(t).detach().double().cpu().reshape(hip.shape[0], -1) for t in (hip, emu, f64))
+    assert hip.shape == emu.shape == f64.shape, (label, hip.shape, emu.shape, f64.shape)
+    assert torch.isfinite(hip).all(), label
+    floor, total, gap = _rms(emu - f64), _rms(hip - f64), _rms(hip - emu)
+    pg, pf = (hip - emu).abs().amax(-1), (emu - f64).abs().amax(-1)
+    st = torch.ones_like(pg, dtype=torch.bool) if stable is None else stable.cpu()
+    r = dict(floor=floor, total=total, gap=gap, gap_p999=float(pg.quantile(0.999)), floor_p999=float(pf.quantile(0.999)),
+             gap_max_stable=float(pg[st].max()) if bool(st.any()) else 0.0, floor_max=float(pf.max()), gap_max=float(pg.max()),
+             n=int(pg.numel()), n_unstable=int((~st).sum()))
+    fail = []
+    if not r['total'] < k_total * floor:
+        fail.append(f"total {r['total']:.2e} >= {k_total} x floor {floor:.2e}")
+    if not r['gap'] < k_gap * floor:
+        fail.append(f"gap {r['gap']:.2e} >= {k_gap} x floor {floor:.2e}")
+    if not r['gap_p999'] < k_p999 * r['floor_p999']:
+        fail.append(f"gap p99.9 {r['gap_p999']:.2e} >= {k_p999} x floor p99.9 {r['floor_p999']:.2e}")
+    if not r['gap_max_stable'] < k_max * r['floor_max']:
+        fail.append(f"gap max (ReLU-stable) {r['gap_max_stable']:.2e} >= {k_max} x floor max {r['floor_max']:.2e}")
+    print(f"PARITY {label:<34} floor {floor:.2e} total {total:.2e} ({total / floor:.2f}) gap {gap:.2e} ({gap / floor:.2f}) | p99.9 gap {r['gap_p999']:.2e} "
+          f"floor {r['floor_p999']:.2e} | max gap {r['gap_max']:.2e}, ReLU-stable {r['gap_max_stable']:.2e} ({r['n_unstable']} of {r['n']} excluded), "
+          f"floor {r['floor_max']:.2e} {'FAIL: ' + '; '.join(fail) if fail else 'ok'}")
+    return r, fail
+
+
+def _shell_points(n, seed=11):
+    """big-pose points near the body's zero set (radius 0.38 .. 0.50 m), the sample of the existing emulation bisect"""
+    g = torch.Generator().manual_seed(seed)
+    d = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1)
+    return d * (0.38 + 0.12 * torch.rand(n, 1, generator=g))
+
+
+def _surface_points(body, n, seed=33):
+    """world points within 2 mm of posed vertices (all inside dist_th) and unit view directions"""
+    g = torch.Generator().manual_seed(seed)
+    vid = torch.randint(0, 6890, (n,), generator=g)
+    wv = (body['pverts'][0].float() @ body['R'][0].float().T + body['Th'][0].float())[vid]
+    x = wv + 0.002 * torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1)
+    v = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1)
+    return x.contiguous(), v.contiguous()
+
+
+def _parity_net(mode, dtype, kind, sd=None, **kw):
+    """a HIP context on the synthetic weights of `kind` (or on `sd`)"""
+    from relightableavatar_amd.networks import make_network
+    dev = _dev()
+    cfg = make_cfg(mode, mlp_dtype=dtype, **kw)
+    net = make_network(cfg)
+    net.load_state_dict(synthetic.make_state_dict(0, relight=mode == 'relight', cfg=cfg, kind=kind) if sd is None else sd)
+    net = net.to(dev).eval()
+    body = synthetic.make_body(0, posed=True)
+    return cfg, net.set_frame(synthetic.to_device(body, dev)), body, dev
+
+
+def _k3_oracle(cfg, sd, dtype, bpts, fr):
+    from oracle import ra_oracle as O
+    with torch.no_grad():
+        emu = O.observed_sdf(O.OracleNet(sd, cfg, emulate=dtype, kernel_like=True), bpts, fr)[:, 0]
+        f64 = O.observed_sdf(O.OracleNet(sd, cfg, emulate='f64acc'), bpts, fr)[:, 0]
+    return emu, f64
+
+
+K3_SIZES = (9000, 20000, 70000)          # 2-, 4- and 8-wave workgroups of the plain distance kernel
+
+
+@pytest.mark.parametrize('kind', ['init', 'sharp'])
+@pytest.mark.parametrize('dtype', ['f16', 'bf16'])
+def test_k3_matches_the_operand_rounding_emulation(dtype, kind):
+    """K3 (launch_mlp_sdf_stream_{f16,bf16}) at all three workgroup widths against the kernel-like emulation of its operand type"""
+    from oracle import ra_oracle as O
+    cfg, eng, body, dev = _parity_net('relight', dtype, kind)
+    sd = synthetic.make_state_dict(0, relight=True, cfg=cfg, kind=kind)
+    bpts = _shell_points(max(K3_SIZES))
+    emu, f64 = _k3_oracle(cfg, sd, dtype, bpts, O._frame(body))
+    fails = []
+    for n in K3_SIZES:
+        eng.reset_counters()
+        hip = eng.observed_sdf(bpts[:n].to(dev)).cpu()
+        c = eng.counters()
+        assert c.n_fine_sdf == n and c.n_fine_sdf_comp == 0 and (c.n_fine_sdf_wide > 0) == (n > 65536), (n, dict(c))
+        fails += rounding_parity(f'K3 sdf {dtype} {kind} n={n}', 'sdf', hip, emu[:n], f64[:n])[1]
+    assert not fails, fails
+
+
+def _k4_oracle(cfg, sd, dtype, fr, bpts=None, x=None, v=None, th=None):
+    """(emulation, f64acc) of the full query: on big-pose points (sdf, grad, feat, relu_margin) or on world points (raw, relu_margin)"""
+    from oracle import ra_oracle as O
+    emu_net = O.OracleNet(sd, cfg, emulate=dtype, kernel_like=True, emulate_backward=True)
+    f64_net = O.OracleNet(sd, cfg, emulate='f64acc')
+    if bpts is not None:
+        e = O.bigpose_query(emu_net, bpts, fr.cond)
+        f = O.bigpose_query(f64_net, bpts, fr.cond)
+        return (e[3][:, 0], e[5], e[4], emu_net.relu_margin), (f[3][:, 0], f[5], f[4])
+    raw_e, out_e = O.network_forward(emu_net, x, v, fr, th)
+    margin = torch.full((x.shape[0],), float('inf'))
+    margin[out_e.mask] = emu_net.relu_margin
+    raw_f, _ = O.network_forward(f64_net, x, v, fr, th)
+    return (raw_e, margin), raw_f
+
+
+def _q(t, dtype):
+    return t.to(torch.float16 if dtype == 'f16' else torch.bfloat16).float()
+
+
+@pytest.mark.parametrize('kind', ['init', 'sharp'])
+@pytest.mark.parametrize('dtype', ['f16', 'bf16'])
+@pytest.mark.parametrize('mode', ['relight', 'anisdf'])
+def test_k4_matches_the_operand_rounding_emulation(mode, dtype, kind):
+    """K4 (launch_mlp_fwd_tape_* + launch_mlp_bwd_heads_*) against the kernel-like emulation of forward AND backward pass.
+    debug_full (the DBG instantiations): d sdf / d bpts un-normalised, sdf, the features as the heads read them (rounded to the
+    operand type).  eng.forward (the production instantiations) on world points with real view directions: world normal,
+    albedo / roughness or rgb, occupancy."""
+    from oracle import ra_oracle as O
+    cfg, eng, body, dev = _parity_net(mode, dtype, kind)
+    sd = synthetic.make_state_dict(0, relight=mode == 'relight', cfg=cfg, kind=kind)
+    fr = O._frame(body)
+    fails = []
+    bpts = _shell_points(20000)
+    (sdf_e, grad_e, feat_e, margin), (sdf_f, grad_f, feat_f) = _k4_oracle(cfg, sd, dtype, fr, bpts=bpts)
+    stable = margin > STABLE_MARGIN
+    grad, sdf, feat, _ = eng.debug_full(bpts.to(dev))
+    lab = f'{mode} {dtype} {kind}'
+    fails += rounding_parity(f'K4 grad {lab}', 'grad', grad.cpu(), grad_e, grad_f, stable)[1]
+    fails += rounding_parity(f'K4 sdf {lab}', 'sdf', sdf.cpu(), sdf_e, sdf_f)[1]
+    fails += rounding_parity(f'K4 feat {lab}', 'feat', feat.cpu(), _q(feat_e, dtype), feat_f)[1]
+    x, v = _surface_points(body, 4000)
+    th = 0.005
+    (raw_e, margin), raw_f = _k4_oracle(cfg, sd, dtype, fr, x=x, v=v, th=th)
+    raw = eng.forward(x.to(dev), v.to(dev), th).cpu()
+    assert bool(torch.isfinite(margin).all()), 'every world point is a fine point'
+    groups = (('normal', slice(13, 16)), ('albedo+rough', slice(9, 13)), ('occ', slice(16, 17))) if mode == 'relight' else \
+        (('normal', slice(9, 12)), ('rgb', slice(12, 15)), ('occ', slice(15, 16)))
+    for name, cols in groups:
+        fails += rounding_parity(f'K4 {name} {lab}', name, raw[:, cols], raw_e[:, cols], raw_f[:, cols], margin > STABLE_MARGIN)[1]
+    assert not fails, fails
+
+
+def test_k4_sub_batches_are_bit_identical():
+    """cfg.k4_batch_slots: the full query in launch pairs of that many fine slots sharing one tape (ragged slot0: the tape is indexed from
+    each sub-batch's first slot) — every point's raw channels as in one batch, bit for bit"""
+    body = synthetic.make_body(0, posed=True)
+    x, v = _surface_points(body, 2100)
+    th = 0.005
+    _, eng, _, dev = _parity_net('relight', 'f16', 'init')
+    c0 = eng.counters().n_fine_full
+    whole = eng.forward(x.to(dev), v.to(dev), th).cpu()
+    assert eng.counters().n_fine_full - c0 == 2100
+    for slots in (32, 257, 300, 1024):
+        _, eng, _, dev = _parity_net('relight', 'f16', 'init', k4_batch_slots=slots)
+        part = eng.forward(x.to(dev), v.to(dev), th).cpu()
+        assert torch.equal(part, whole), (slots, float((part - whole).abs().max()))
+
+
+def test_compensated_query_ignores_the_operand_type():
+    """K3C / K3CC (trace_precision 2: every distance query compensated) use IEEE-half hi + lo pairs whatever cfg.mlp_dtype says (ra_pack.cpp
+    builds sarena_c from f16 pairs): an f16 and a bf16 context give the same bits, at sizes that take K3CC (<= 8 Ki points) and K3C"""
+    bpts = _shell_points(20000)
+    out = {}
+    for dtype in ('f16', 'bf16'):
+        _, eng, _, dev = _parity_net('relight', dtype, 'init', trace_precision=2)
+        eng.reset_counters()
+        out[dtype] = [eng.observed_sdf(bpts[:n].to(dev)).cpu() for n in (5000, 20000)]
+        assert eng.counters().n_fine_sdf_comp == 25000
+    for a, b in zip(out['f16'], out['bf16']):
+        assert torch.equal(a, b), float((a - b).abs().max())
+
+
+def test_frame_relight_smooth_bf16(golden):
+    """frame_relight_smooth with bf16 operands: the surface trace runs in the compensated tier (K3C, f16 pairs) in both operand types,
+    so the traced surface and the hit mask are those of the f16 frame; the shadow rays take plain bf16 K3; rgb / shade / normals
+    within 1 dB of the committed bf16 precision floor (tests/golden/precision_floor.json, the kernel-like emulation's own figures)"""
+    from relightableavatar_amd.renderer import make_renderer
+    ref = golden('frame_relight_smooth.npz')
+    outs = {}
+    for dtype in ('f16', 'bf16'):
+        cfg, net, dev = build('relight', dtype=dtype, vis_specular_map=True)
+        batch = synthetic.to_device(synthetic.make_batch(int(ref['H']), int(ref['H']), seed=0, posed=True, crop=int(ref['crop']),
+                                                         skin_noise=float(ref['skin_noise'])), dev)
+        net.engine().reset_counters()
+        outs[dtype] = make_renderer(cfg, net).render(batch)
+        c = net.engine().counters()
+        assert 0 < c.n_fine_sdf_comp < c.n_fine_sdf and c.n_fine_full > 0, dict(c)       # plain K3 (the shadow rays) and K4 ran
+    a, b = outs['f16'], outs['bf16']
+    assert torch.equal(a.acc_map, b.acc_map) and torch.equal(a.surf_map, b.surf_map)
+    floor = floor_of('frame_relight_smooth.npz', 'bf16')
+    for k in ('rgb_map', 'shade_map', 'norm_map'):
+        p = psnr(b[k], ref[k])
+        print(f'frame_relight_smooth bf16 {k}: PSNR {p:.2f} dB (floor {floor[k]["psnr"]:.2f}), f16 frame {psnr(a[k], ref[k]):.2f} dB')
+        assert p >= floor[k]['psnr'] - 1.0, (k, p, floor[k]['psnr'])
+
+
+def truncated_state_dict(sd, dtype, which):
+    """the weights of the MLP layers named by `which` (key prefixes) pre-truncated TOWARDS ZERO to the operand type — what a kernel
+    that truncated instead of rounding to nearest would compute with.  Weight-normed layers: weight_v = the truncated folded weight,
+    weight_g = its row norms (the packer folds before it rounds, so it then packs the truncated values unchanged)."""
+    import numpy as np
+    from oracle.ra_oracle import fold_weight_norm
+
+    def trunc(w):
+        w = w.float()
+        if dtype == 'bf16':
+            return (w.contiguous().view(torch.int32) & -65536).view(torch.float32)
+        h = w.numpy().astype(np.float16)
+        away = np.abs(h.astype(np.float32)) > np.abs(w.numpy())
+        h[away] = np.nextafter(h[away], np.float16(0))
+        return torch.from_numpy(h.astype(np.float32))
+    out = dict(sd)
+    for k in sd:
+        if not any(k.startswith(p) for p in which):
+            continue
+        if k.endswith('.weight_v'):
+            g = k[:-len('_v')] + '_g'
+            wt = trunc(fold_weight_norm(sd[g].float(), sd[k].float()))
+            out[k], out[g] = wt, wt.norm(dim=1, keepdim=True).reshape(sd[g].shape)
+        elif k.endswith('.weight'):
+            out[k] = trunc(sd[k])
+    return out
+
+
+MUTATIONS = {       # smallest first
+    'sdf lin2': ('signed_distance_network.mlp.lin2.',),
+    'resd linear2': ('residual_deformation_network.mlp.linears.2.',),
+    'all MLP layers': ('signed_distance_network.', 'residual_deformation_network.', 'render_network.', 'albedo_network.', 'roughness_network.'),
+}
+
+
+@pytest.mark.parametrize('dtype', ['f16', 'bf16'])
+def test_rounding_parity_rejects_truncated_weights(dtype):
+    """sensitivity of rounding_parity: the HIP side on weights truncated towards zero (an error of the operand rounding's own size, biased),
+    the emulation on the true weights — the criterion must reject it, for K3 and K4.  Reports which mutations it catches."""
+    from oracle import ra_oracle as O
+    cfg = make_cfg('relight', mlp_dtype=dtype)
+    sd = synthetic.make_state_dict(0, relight=True, cfg=cfg)
+    body = synthetic.make_body(0, posed=True)
+    fr = O._frame(body)
+    bpts = _shell_points(20000)
+    emu3, f643 = _k3_oracle(cfg, sd, dtype, bpts, fr)
+    (_, grad_e, _, margin), (_, grad_f, _) = _k4_oracle(cfg, sd, dtype, fr, bpts=bpts)
+    caught = {}
+    for name, which in MUTATIONS.items():
+        _, eng, _, dev = _parity_net('relight', dtype, 'init', sd=truncated_state_dict(sd, dtype, which))
+        f3 = rounding_parity(f'mutated ({name}) K3 sdf {dtype}', 'sdf', eng.observed_sdf(bpts.to(dev)).cpu(), emu3, f643)[1]
+        grad = eng.debug_full(bpts.to(dev))[0].cpu()
+        f4 = rounding_parity(f'mutated ({name}) K4 grad {dtype}', 'grad', grad, grad_e, grad_f, margin > STABLE_MARGIN)[1]
+        caught[name] = (bool(f3), bool(f4))
+    print(f'truncated weights, {dtype}: caught (K3, K4): {caught}')
+    # measured: one truncated SDF-net layer is caught by both; one truncated residual-net layer by K4's gradient (gap 0.60-0.62 of the
+    # floor) but not by the distance (0.55-0.63)
+    assert caught['all MLP layers'] == (True, True) and caught['sdf lin2'] == (True, True) and caught['resd linear2'][1], caught

@@ -117,3 +117,96 @@ def test_fp32_unstable_rays_fixture_is_reproducible():
         st, _ = O.surface_trace(net, synthetic.make_batch(128, 128, seed=0, posed=True, crop=8), 1e-7, torch.Generator().manual_seed(s))
         moved += int((st - st0).abs()[bad].max() > 1e-3)
     assert moved >= 1
+
+
+def _shell(n, seed=11):
+    g = torch.Generator().manual_seed(seed)
+    d = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1)
+    return d * (0.38 + 0.12 * torch.rand(n, 1, generator=g))
+
+
+def test_backward_emulation_is_opt_in_and_changes_only_the_gradient():
+    """emulate_backward off: no custom autograd function is involved (the existing paths, bit for bit); on: the forward values are the
+    same bits, only d sdf / d bpts changes — by less than the rounding floor itself"""
+    cfg, sd = _nets()
+    fr = O._frame(synthetic.make_body(0, posed=True))
+    x = _shell(2000)
+    rms = lambda a: float(a.pow(2).mean().sqrt())
+    g64 = O.bigpose_query(O.OracleNet(sd, cfg, emulate='f64acc'), x, fr.cond)[5]
+    for dt in ('f16', 'bf16'):
+        off = O.OracleNet(sd, cfg, emulate=dt, kernel_like=True)
+        on = O.OracleNet(sd, cfg, emulate=dt, kernel_like=True, emulate_backward=True)
+        a, b = O.bigpose_query(off, x, fr.cond), O.bigpose_query(on, x, fr.cond)
+        assert off.relu_margin is None and off.delta_stats == {} and on.relu_margin.shape == (2000,) and on.delta_stats['n_nonzero'] > 0
+        for k in range(5):                                  # bpts, resd, cpts, sdf, feat
+            assert torch.equal(a[k], b[k]), (dt, k)
+        assert 0 < rms(b[5] - a[5]) < rms(a[5] - g64), dt
+    # the fp32 reference path takes plain autograd: d sdf / d bpts of observed_sdf
+    net = O.OracleNet(sd, cfg)
+    xr = x.clone().requires_grad_(True)
+    ref = torch.autograd.grad(O.observed_sdf(net, xr, fr).sum(), xr)[0]
+    assert torch.equal(O.bigpose_query(net, x, fr.cond)[5], ref)
+    for bad in (dict(emulate='f16'), dict(emulate=None, kernel_like=True), dict(emulate='f16x2', kernel_like=True), dict(emulate='f64acc')):
+        try:
+            O.OracleNet(sd, cfg, emulate_backward=True, **bad)
+        except ValueError:
+            continue
+        raise AssertionError(bad)
+
+
+def test_backward_emulation_building_blocks():
+    """the three autograd pieces against their definitions: the transposed product rounds delta * GRAD_SCALE and nothing else; sigma'
+    comes from the ROUNDED scaled activation (1 - 2^-q(y')); the ReLU mask from the sign bit"""
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(64, 40, generator=g).requires_grad_(True)
+    w = torch.randn(24, 40, generator=g)
+    up = torch.randn(64, 24, generator=g) * 1e-3
+    stats = {}
+    y = O._KernelTransposedProduct.apply(x, (x @ w.T).detach(), w, torch.float16, stats)
+    gx = torch.autograd.grad(y, x, up)[0]
+    q = (up * O.GRAD_SCALE).half().float() / O.GRAD_SCALE
+    assert torch.equal(gx, q @ w) and not torch.equal(q, up) and stats['max_abs'] == float((up * O.GRAD_SCALE).abs().max())
+    y = O._KernelTransposedProduct.apply(x, (x @ w.T).detach(), w, None, None)          # the SDF head's seed: fp32
+    assert torch.equal(torch.autograd.grad(y, x, up)[0], up @ w)
+    z = (torch.randn(5000, generator=g) * 0.03).requires_grad_(True)
+    for dt in (torch.float16, torch.bfloat16):
+        gz = torch.autograd.grad(O._TapedSoftplus.apply(z, dt).sum(), z)[0]
+        yq = (O.softplus100(z.detach()) * O.OracleNet.SP_SCALE).to(dt).float()
+        assert torch.equal(gz, 1 - torch.exp2(-yq))
+        exact = torch.sigmoid(100 * z.detach())
+        ulp = torch.finfo(dt).eps
+        assert 0 < float((gz - exact).abs().max()) < 2 * ulp * float(yq.abs().max()), dt        # the rounding of y' is all that differs
+    z = torch.tensor([-1.0, -0.0, 0.0, 1e-30, -1e-30, 2.0], requires_grad=True)
+    assert torch.autograd.grad(O._SignMaskRelu.apply(z).sum(), z)[0].tolist() == [0, 0, 1, 1, 0, 1]
+
+
+# d sdf / d bpts with the reverse pass emulated, rms against the float64-accumulated oracle on 4 000 near-surface points (measured:
+# f16 6.6e-4 / 2.3e-3, bf16 2.9e-3 / 7.7e-3 at init / sharp weights)
+GRAD_BANDS = {('f16', 'init'): (5e-4, 8.5e-4), ('bf16', 'init'): (2.3e-3, 3.7e-3),
+              ('f16', 'sharp'): (1.8e-3, 2.9e-3), ('bf16', 'sharp'): (6e-3, 9.5e-3)}
+
+
+def test_backward_emulation_error_bands():
+    """the floor the reverse-mode kernel K4 is held to (tests/test_gpu_parity.py rounding_parity): the emulated gradient's error against
+    f64acc in a measured band per operand type and weights, bf16 several times f16; at trained-like weights no scaled delta overflows f16
+    (K4 carries gradients times GRAD_SCALE = 16 for headroom against underflow)"""
+    fr = O._frame(synthetic.make_body(0, posed=True))
+    cfg = make_cfg('relight')
+    x = _shell(4000)
+    rms = lambda a: float(a.pow(2).mean().sqrt())
+    got = {}
+    for kind in ('init', 'sharp'):
+        sd = synthetic.make_state_dict(0, relight=True, cfg=cfg, kind=kind)
+        g64 = O.bigpose_query(O.OracleNet(sd, cfg, emulate='f64acc'), x, fr.cond)[5]
+        for dt in ('f16', 'bf16'):
+            net = O.OracleNet(sd, cfg, emulate=dt, kernel_like=True, emulate_backward=True)
+            e = rms(O.bigpose_query(net, x, fr.cond)[5] - g64)
+            st = net.delta_stats
+            print(f'{dt} {kind}: grad rms vs f64acc {e:.2e}; largest |delta * 16| {st["max_abs"]:.3g}, '
+                  f'{100 * st["n_subnormal"] / st["n_nonzero"]:.2f} % of the nonzero scaled deltas below the smallest normal {dt}')
+            lo, hi = GRAD_BANDS[(dt, kind)]
+            assert lo < e < hi, (dt, kind, e)
+            assert st['max_abs'] < 65504 / 16, (dt, kind, st)          # four more octaves of headroom than the scale needs
+            got[(dt, kind)] = e
+    for kind in ('init', 'sharp'):
+        assert got[('bf16', kind)] > 3 * got[('f16', kind)], got
