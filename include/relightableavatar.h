@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RA_ABI_VERSION 8
+#define RA_ABI_VERSION 9
 #define RA_N_LIGHTS_MAX 512 /* env_h * env_w = 16 * 32 (lib/config/config.py:111-112) */
 
 typedef struct ra_ctx ra_ctx;
@@ -267,6 +267,22 @@ int ra_reshade(ra_ctx* ctx, const float* ray_o, const float* surf, const float* 
                const float* albedo, const float* roughness, const float* lvis, const float* ldot,
                int P, const float* probes_dev, int n_probes, int probe_h, int probe_w,
                float* rgb, float* shade, float* spec, void* stream);
+
+/* Backward of ra_reshade with respect to albedo, roughness and the probes — the relighting stage's gradient (relight_trainer.py:113-118:
+ * geometry frozen, light visibility under no_grad, the image loss reaches the shading sum only).  d_rgb: n_probes x P x 3, the gradient
+ * with respect to the tone-mapped rgb that ra_reshade returns.  d_albedo: P x 3, summed over the probes (the Lambert term; exactly 0
+ * under glossy_only).  d_roughness: P, summed over probes and channels (through rough^4 in D and G; exactly 0 under lambert_only).
+ * d_probes: n_probes x probe_h x probe_w x 3 (the bilinear taps of the probe lookup, transposed, summed over pixels and lights).
+ * Conventions are torch autograd's on render_human (:21-66): the sRGB clip passes gradient for 0 <= lin <= 1 only, an operand that
+ * safe_divide clamps gets none, chi factors and the clips of l.n / v.n are constants; surf, norm, ray_o, lvis and ldot are constants
+ * (ldot is not read: cancel_cosine).  lambert_only / glossy_only come from the ctx config.  Any output may be NULL; outputs are
+ * overwritten, not accumulated into.  P == 0 or n_probes == 0 returns 0 and writes nothing.  A probe must fit the kernel's LDS tile:
+ * probe_h * probe_w <= 5461 (16 x 32 and 32 x 64 do).  Asynchronous on stream; allocates ctx scratch on the first call of a size only.
+ * Every output is bit-identical from run to run, and a probe's gradient does not depend on which other probes share the call. */
+int ra_reshade_backward(ra_ctx* ctx, const float* ray_o, const float* surf, const float* norm,
+                        const float* albedo, const float* roughness, const float* lvis, const float* ldot, int P,
+                        const float* probes_dev, int n_probes, int probe_h, int probe_w,
+                        const float* d_rgb, float* d_albedo, float* d_roughness, float* d_probes, void* stream);
 
 /* novel_light_sphere_tracing.render_ground (:70-99): re-shade the ground layer of the main pass under n_probes probes from its
  * cached per-light visibility and cosine (ra_ground_out.lvis / .ldot of ALL frame pixels, P x 512 each): Lambert ground,

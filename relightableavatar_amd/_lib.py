@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RA_LIB_PATH') or os.path.join(_HERE, 'librelightableavatar_hip.so')    # override: kernel experiments (tools/)
 _lib = None
-ABI_VERSION = 8          # RA_ABI_VERSION of include/relightableavatar.h
+ABI_VERSION = 9          # RA_ABI_VERSION of include/relightableavatar.h
 
 
 class RaError(RuntimeError):
@@ -114,6 +114,7 @@ SYMBOLS = {
                                          C.POINTER(ra_ground_params), C.POINTER(ra_ground_out), C.c_void_p]),
     'ra_blend_ground': (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'ra_reshade': (C.c_int, [C.c_void_p] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    'ra_reshade_backward': (C.c_int, [C.c_void_p] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'ra_k3cc_enabled': (C.c_int, [C.c_void_p]),
     'ra_begin_render': (C.c_int, [C.c_void_p]),
     'ra_debug_key_lights': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1036,6 +1036,36 @@ int ra_reshade(ra_ctx* c, const float* ray_o, const float* surf, const float* no
     return 0;
 }
 
+int ra_reshade_backward(ra_ctx* c, const float* ray_o, const float* surf, const float* norm, const float* albedo, const float* roughness,
+                        const float* lvis, const float* ldot, int P, const float* probes, int n_probes, int ph, int pw,
+                        const float* d_rgb, float* d_albedo, float* d_roughness, float* d_probes, void* stream) {
+    RA_CHECK(c && c->have_weights && c->cfg.relight, "ra_reshade_backward: needs a relight ctx with weights");
+    RA_CHECK(P >= 0 && n_probes >= 0, "ra_reshade_backward: bad sizes");
+    if (P == 0 || n_probes == 0) return 0;
+    RA_CHECK(ray_o && surf && norm && albedo && roughness && lvis && ldot && probes && d_rgb, "ra_reshade_backward: null input");
+    RA_CHECK(ph > 0 && pw > 0 && shade_bwd_probes_per_launch(ph, pw) >= 1, "ra_reshade_backward: the probe does not fit the kernel's LDS tile (h * w <= 5461)");
+    RA_HIP(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    ShadeBwd a{};
+    a.ray_o = ray_o; a.surf = surf; a.norm = norm; a.albedo = albedo; a.rough = roughness; a.lvis = lvis;      // ldot: cancel_cosine, rgb does not read it
+    a.light_xyz = c->light_xyz.as<float>(); a.light_area = c->light_area.as<float>(); a.L = c->n_lights;
+    a.probes = probes; a.n_probes = n_probes; a.ph = ph; a.pw = pw; a.d_rgb = d_rgb; a.P = P;
+    a.d_albedo = d_albedo; a.d_rough = d_roughness; a.d_probes = d_probes;
+    if (d_probes) {      // one partial slab per workgroup: grown on the first call of a size, reused afterwards
+        int err = 0;
+        const int per = shade_bwd_probes_per_launch(ph, pw);
+        a.slabs = c->buf<float>("rsb_slabs", (size_t)shade_bwd_grid(P) * (per < n_probes ? per : n_probes) * ph * pw * 3, &err);
+        if (err) return 1;
+    }
+    ra_config cfg = c->cfg;      // ra_reshade's configuration
+    cfg.tonemapping = 1;
+    cfg.only_visibility = 0;
+    cfg.vis_shade_map = 0;
+    launch_shade_bwd(a, cfg, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
 int ra_reshade_ground(ra_ctx* c, const float* ray_d, const float* albedo_map, const float* lvis, const float* ldot, int P,
                       const float* probes, int n_probes, int ph, int pw, const float* images, int ih, int iw, int attach_envmap,
                       float* rgb, float* albedo, float* shade, float* spec, void* stream) {

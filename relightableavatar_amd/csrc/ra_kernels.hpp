@@ -162,6 +162,23 @@ struct ShadeIn {
 };
 void launch_shade(const ShadeIn& in, const ra_config& cfg, hipStream_t s);
 
+// backward of the re-shade (ra_shade_bwd.hip): d rgb -> d albedo, d roughness, d probes; pixel indexed, all P pixels live
+constexpr int SHADE_BWD_MAX_GRID = 768;          // workgroups (= partial slabs) at most; the grid depends on P alone
+constexpr size_t SHADE_BWD_LDS_BYTES = 65536;    // LDS budget of the probe tiles of one launch
+struct ShadeBwd {
+    const float *ray_o, *surf, *norm, *albedo, *rough;   // P x 3 / P
+    const float* lvis;                                    // P x L
+    const float *light_xyz, *light_area; int L;
+    const float* probes; int n_probes, ph, pw;            // any number of probes: several launches
+    const float* d_rgb;                                   // n_probes x P x 3
+    int P;
+    float *d_albedo, *d_rough, *d_probes;                 // P x 3, P, n_probes x ph x pw x 3; nullable; overwritten
+    float* slabs;                                         // shade_bwd_grid(P) x shade_bwd_probes_per_launch(ph, pw) x (ph pw 3) floats (needed with d_probes)
+};
+int shade_bwd_grid(int P);
+int shade_bwd_probes_per_launch(int ph, int pw);          // 0: one probe's tile does not fit the LDS budget
+void launch_shade_bwd(const ShadeBwd& a, const ra_config& cfg, hipStream_t s);
+
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot
 void launch_scatter_maps(const int* hit_idx, const int* hit_count, int P, int premultiply, const float* acc_full,

@@ -316,6 +316,24 @@ class Engine:
                                   _ptr(rgb), _ptr(shade), _ptr(spec), self.stream), 'ra_reshade')
         return rgb, shade, spec
 
+    def reshade_backward(self, ray_o, surf, norm, albedo, rough, lvis, ldot, probes, d_rgb, want=(True, True, True)):
+        """backward of reshade's rgb: d_rgb (n,P,3) -> d_albedo (P,3), d_rough (P,), d_probes (n,h,w,3); want: which of the three
+        to compute (the others are None)."""
+        d = self.device
+        a = [_f32(t, d) for t in (ray_o.reshape(-1, 3), surf.reshape(-1, 3), norm.reshape(-1, 3), albedo.reshape(-1, 3), rough.reshape(-1))]
+        P = a[0].shape[0]
+        lvis, ldot = _f32(lvis.reshape(P, -1), d), _f32(ldot.reshape(P, -1), d)
+        probes = _f32(probes, d)
+        n, ph, pw = probes.shape[0], probes.shape[1], probes.shape[2]
+        d_rgb = _f32(d_rgb.reshape(n, P, 3), d)
+        # zeros, not empty: a call with P == 0 or n == 0 writes nothing, and the gradient of an empty sum is 0
+        d_alb = torch.zeros(P, 3, device=d) if want[0] else None
+        d_rgh = torch.zeros(P, device=d) if want[1] else None
+        d_prb = torch.zeros(n, ph, pw, 3, device=d) if want[2] else None
+        check(self.lib.ra_reshade_backward(self.ctx, *[_ptr(t) for t in a], _ptr(lvis), _ptr(ldot), P, _ptr(probes), n, ph, pw,
+                                           _ptr(d_rgb), _ptr(d_alb), _ptr(d_rgh), _ptr(d_prb), self.stream), 'ra_reshade_backward')
+        return d_alb, d_rgh, d_prb
+
     # ------------------------------------------------------------------ measurement
     def counters(self) -> dotdict:
         c = ra_counters()

@@ -51,3 +51,29 @@ def gen_light_xyz(env_h: int, env_w: int, env_r: float):
     sin_colat = torch.sin(math.pi / 2 - lats)
     area = 4 * math.pi * sin_colat / torch.sum(sin_colat)
     return xyz, area
+
+
+class _Reshade(torch.autograd.Function):
+    """rgb of Engine.reshade with its gradient: forward = ra_reshade, backward = ra_reshade_backward"""
+
+    @staticmethod
+    def forward(ctx, eng, ray_o, surf, norm, albedo, rough, lvis, ldot, probes):
+        rgb, _, _ = eng.reshade(ray_o, surf, norm, albedo, rough, lvis, ldot, probes, want_spec=False)
+        ctx.eng = eng
+        ctx.save_for_backward(ray_o, surf, norm, albedo, rough, lvis, ldot, probes)
+        return rgb
+
+    @staticmethod
+    def backward(ctx, d_rgb):
+        ray_o, surf, norm, albedo, rough, lvis, ldot, probes = ctx.saved_tensors
+        want = tuple(ctx.needs_input_grad[i] for i in (4, 5, 8))
+        d_alb, d_rgh, d_prb = ctx.eng.reshade_backward(ray_o, surf, norm, albedo, rough, lvis, ldot, probes, d_rgb, want=want)
+        shaped = lambda g, like: None if g is None else g.reshape(like.shape).to(like.dtype)
+        return (None, None, None, None, shaped(d_alb, albedo), shaped(d_rgh, rough), None, None, shaped(d_prb, probes))
+
+
+def reshade(eng, ray_o, surf, norm, albedo, rough, lvis, ldot, probes):
+    """Differentiable novel-light re-shade (novel_light_sphere_tracing.render_human :21-66): probes (n,h,w,3) -> rgb (n,P,3).
+    Gradients reach albedo, rough and probes only — the relighting stage's (relight_trainer.py:113-118): geometry is frozen and the
+    light visibility was computed without gradients.  Engine.reshade is the plain (no-autograd) call."""
+    return _Reshade.apply(eng, ray_o, surf, norm, albedo, rough, lvis, ldot, probes)

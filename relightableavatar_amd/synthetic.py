@@ -412,6 +412,44 @@ def make_novel_lights(n: int, seed: int = 0, env_h: int = 16, env_w: int = 32) -
     return lights
 
 
+# the cases of tests/golden/reshade_grad.npz (make_golden_grad.py): name -> configuration switches, probe size, probes, roughness range
+# ("conditioned" [0.3, 0.99] / "full" [0.09, 0.99]: down to the reference's roughness_bias floor, where a few grazing low-roughness pixels
+# dominate a gradient's maximum), probe scale (12: about half the pixels leave the tone map's [0, 1])
+RESHADE_GRAD_P = 96
+RESHADE_GRAD_CASES = {
+    'default': dict(cfg={}, probe_hw=(16, 32), n_probes=1, rough=(0.3, 0.99), scale=1.0),
+    'default_full': dict(cfg={}, probe_hw=(16, 32), n_probes=1, rough=(0.09, 0.99), scale=1.0),
+    'lambert_only': dict(cfg={'lambert_only': True}, probe_hw=(16, 32), n_probes=1, rough=(0.3, 0.99), scale=1.0),
+    'glossy_only': dict(cfg={'glossy_only': True}, probe_hw=(16, 32), n_probes=1, rough=(0.3, 0.99), scale=1.0),
+    'glossy_only_full': dict(cfg={'glossy_only': True}, probe_hw=(16, 32), n_probes=1, rough=(0.09, 0.99), scale=1.0),
+    'probe_32x64': dict(cfg={}, probe_hw=(32, 64), n_probes=1, rough=(0.3, 0.99), scale=1.0),
+    'two_probes': dict(cfg={}, probe_hw=(16, 32), n_probes=2, rough=(0.09, 0.99), scale=1.5),
+    'bright': dict(cfg={}, probe_hw=(16, 32), n_probes=1, rough=(0.3, 0.99), scale=12.0),
+}
+
+
+def make_reshade_inputs(seed: int, P: int, probe_hw=(16, 32), n_probes: int = 1, rough=(0.3, 0.99), scale: float = 1.0, L: int = 512) -> dotdict:
+    """cached maps of P pixels as the re-shade reads them, with normals roughly facing the camera, plus probes and a d_rgb: host fp32.
+    ray_o, surf, norm, albedo (P,3); rough (P,); lvis, ldot (P,L); probes (n,h,w,3); d_rgb (n,P,3)."""
+    g = torch.Generator().manual_seed(1000 + seed)
+    ray_o = torch.randn(P, 3, generator=g) * 0.05 + torch.tensor([0.0, 0.0, -2.0])
+    surf = (torch.rand(P, 3, generator=g) - 0.5) * 0.6
+    to_cam = torch.nn.functional.normalize(ray_o - surf, dim=-1)
+    norm = torch.nn.functional.normalize(to_cam + 0.5 * torch.randn(P, 3, generator=g), dim=-1)
+    albedo = torch.rand(P, 3, generator=g) * 0.9 + 0.05
+    rgh = torch.rand(P, generator=g) * (rough[1] - rough[0]) + rough[0]
+    lvis = torch.rand(P, L, generator=g)
+    ldot = torch.rand(P, L, generator=g) * 2 - 1
+    probes = torch.rand(n_probes, probe_hw[0], probe_hw[1], 3, generator=g) * scale
+    d_rgb = torch.randn(n_probes, P, 3, generator=g)
+    return dotdict(ray_o=ray_o, surf=surf, norm=norm, albedo=albedo, rough=rgh, lvis=lvis, ldot=ldot, probes=probes, d_rgb=d_rgb)
+
+
+def reshade_case_inputs(name: str) -> dotdict:
+    c = RESHADE_GRAD_CASES[name]
+    return make_reshade_inputs(list(RESHADE_GRAD_CASES).index(name), RESHADE_GRAD_P, c['probe_hw'], c['n_probes'], c['rough'], c['scale'])
+
+
 def to_device(batch, device):
     """the loader's hand-over (the reference's to_cuda(batch)); small per-frame constants the host needs again (the body's
     bounding box the renderer grows per chunk) keep a host mirror, so the render loop never reads them back from the device"""
