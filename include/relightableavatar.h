@@ -284,6 +284,39 @@ int ra_reshade_backward(ra_ctx* ctx, const float* ray_o, const float* surf, cons
                         const float* probes_dev, int n_probes, int probe_h, int probe_w,
                         const float* d_rgb, float* d_albedo, float* d_roughness, float* d_probes, void* stream);
 
+/* The material heads of the relighting stage on cached surface features: forward and weight gradient (relight_network.py:45-47,91-104:
+ * albedo_network 256 -> 128 -> 128 -> 3, roughness_network 256 -> 128 -> 128 -> 1, Softplus(beta = 100), output slope * sigmoid + bias with
+ * the slopes and biases of the ctx config).  With ra_reshade_backward this closes the chain photograph -> d_albedo / d_roughness -> head
+ * weights on the device (relight_trainer.py:113-118 trains exactly these two networks and the probe; geometry is frozen).
+ *
+ * Parameters are ONE flat fp32 device vector theta of ra_heads_param_count() = 99 332 floats in torch's own row-major layout:
+ *   albedo_network.linears.0.weight (128 x 256), .0.bias (128), .1.weight (128 x 128), .1.bias (128), .2.weight (3 x 128), .2.bias (3),
+ *   then roughness_network likewise with .2.weight (1 x 128), .2.bias (1).
+ * d_theta has the same layout.  Width 128 and depth 2 are compiled in.  Writing fitted weights back needs no call of its own: download
+ * theta, split it into the twelve state_dict keys, ra_set_weight them and ra_finalize_weights again.
+ *
+ * The kernels always use f16 operands with fp32 accumulation, whatever ra_config.mlp_f16 says (bf16 operands leave the weight gradient
+ * 7-13 x noisier).  The deltas of the backward pass are normalised per call and per head by a power of two found on the device and
+ * unscaled in fp32: the result is linear in the incoming gradient down to gradients of 1e-12 and below.
+ *
+ * ra_heads_get_params: the heads as loaded by ra_set_weight, in the flat layout (a set-up call: it waits for its copy on stream).
+ * ra_heads_forward:    feat (n x 256) -> albedo (n x 3), roughness (n); either output may be NULL.
+ * ra_heads_backward:   d_albedo (n x 3), d_roughness (n) -> d_theta.  Either gradient may be NULL: its head's slice of d_theta is written
+ *                      as zeros, and the other head's slice is bit-identical to what it is with both given.  The forward is recomputed.
+ * ra_bigpose_features: the K4 forward on big-pose points of the CURRENT frame (channels 3:6 of ra_render_out.raw), returning the 256
+ *                      features as the heads see them inside the renderer (f16 values); bit-identical to ra_debug_mlp's feat.
+ *
+ * Asynchronous on stream; outputs are overwritten; n == 0 returns 0 and writes nothing; a null required input is the error "null input",
+ * a ctx that is not a relight ctx with weights the error "relight ctx".  Scratch is allocated on the first call of a size only.  No float
+ * atomics: partial sums go to one slab per workgroup and are added in slab order, the grid depends on n alone, two identical calls are
+ * bit-identical. */
+size_t ra_heads_param_count(const ra_ctx* ctx);
+int ra_heads_get_params(ra_ctx* ctx, float* theta_dev, void* stream);
+int ra_heads_forward(ra_ctx* ctx, const float* theta_dev, const float* feat_dev, int n, float* albedo_dev, float* rough_dev, void* stream);
+int ra_heads_backward(ra_ctx* ctx, const float* theta_dev, const float* feat_dev, int n,
+                      const float* d_albedo_dev, const float* d_rough_dev, float* d_theta_dev, void* stream);
+int ra_bigpose_features(ra_ctx* ctx, const float* bpts_dev, int n, float* feat_dev, void* stream);
+
 /* novel_light_sphere_tracing.render_ground (:70-99): re-shade the ground layer of the main pass under n_probes probes from its
  * cached per-light visibility and cosine (ra_ground_out.lvis / .ldot of ALL frame pixels, P x 512 each): Lambert ground,
  * rgb = linear2srgb(albedo / pi * sum_l lvis ldot area L_probe(l)), shade = sum / pi, spec = shade / 20 (no shading_albedo, no

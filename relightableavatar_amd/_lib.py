@@ -115,6 +115,10 @@ SYMBOLS = {
     'ra_blend_ground': (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'ra_reshade': (C.c_int, [C.c_void_p] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4),
     'ra_reshade_backward': (C.c_int, [C.c_void_p] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    'ra_heads_get_params': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ra_heads_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ra_heads_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ra_bigpose_features': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'ra_k3cc_enabled': (C.c_int, [C.c_void_p]),
     'ra_begin_render': (C.c_int, [C.c_void_p]),
     'ra_debug_key_lights': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -149,6 +153,11 @@ SYMBOLS = {
     'ra_debug_hdq': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 7 + [C.POINTER(C.c_int), C.c_void_p]),
 }
 
+# ... and the one that does not return int / const char*
+SYMBOLS_SIZE_T = {
+    'ra_heads_param_count': (C.c_size_t, [C.c_void_p]),
+}
+
 
 def build(verbose: bool = False) -> str:
     """compile csrc/ for gfx950 with hipcc (cross-compiles without a GPU)."""
@@ -173,7 +182,7 @@ def lib():
     # loaded before, our library's libamdhip64.so.7 resolves to the copy that is already there.
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_SIZE_T.items()):
         fn = getattr(L, name)      # AttributeError if the header and the library disagree
         fn.restype = res
         fn.argtypes = args

@@ -1066,6 +1066,79 @@ int ra_reshade_backward(ra_ctx* c, const float* ray_o, const float* surf, const 
     return 0;
 }
 
+// ---- the material heads on cached features (ra_heads.hip) ----------------------------------------
+size_t ra_heads_param_count(const ra_ctx*) { return HEADS_PARAMS; }
+
+static int heads_ready(ra_ctx* c, const char* who) {
+    if (!(c && c->have_weights && c->cfg.relight)) { ra_set_error(std::string(who) + ": needs a relight ctx with weights"); return 1; }
+    if (hipSetDevice(c->device) != hipSuccess) { ra_set_error(std::string(who) + ": hipSetDevice failed"); return 1; }
+    return 0;
+}
+
+int ra_heads_get_params(ra_ctx* c, float* theta, void* stream) {
+    if (heads_ready(c, "ra_heads_get_params")) return 1;
+    RA_CHECK(theta, "ra_heads_get_params: null input");
+    std::vector<float>& t = c->heads_theta;
+    t.clear();
+    for (const char* net : {"albedo_network", "roughness_network"})
+        for (int l = 0; l < 3; ++l)
+            for (const char* kind : {"weight", "bias"}) {
+                const std::string key = std::string(net) + ".linears." + std::to_string(l) + "." + kind;
+                auto it = c->state_dict.find(key);
+                RA_CHECK(it != c->state_dict.end(), "ra_heads_get_params: missing " + key);
+                t.insert(t.end(), it->second.begin(), it->second.end());
+            }
+    RA_CHECK(t.size() == (size_t)HEADS_PARAMS, "ra_heads_get_params: the loaded heads are not 256 -> 128 -> 128 -> {3, 1}");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipMemcpyAsync(theta, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    RA_HIP(hipStreamSynchronize(s));      // the staging vector may be rebuilt by the next call
+    return 0;
+}
+
+int ra_heads_forward(ra_ctx* c, const float* theta, const float* feat, int n, float* albedo, float* rough, void* stream) {
+    if (heads_ready(c, "ra_heads_forward")) return 1;
+    RA_CHECK(n >= 0, "ra_heads_forward: bad sizes");
+    if (n == 0) return 0;
+    RA_CHECK(theta && feat, "ra_heads_forward: null input");
+    int err = 0;
+    HeadsIO io{};
+    io.theta = theta; io.feat = feat; io.n = n; io.albedo = albedo; io.rough = rough;
+    io.w16 = c->buf<char>("heads_w16", HEADS_W16_BYTES, &err);
+    if (err) return 1;
+    launch_heads_forward(io, c->cfg, (hipStream_t)stream);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_heads_backward(ra_ctx* c, const float* theta, const float* feat, int n, const float* d_albedo, const float* d_rough, float* d_theta,
+                      void* stream) {
+    if (heads_ready(c, "ra_heads_backward")) return 1;
+    RA_CHECK(n >= 0, "ra_heads_backward: bad sizes");
+    if (n == 0) return 0;
+    RA_CHECK(theta && feat && d_theta, "ra_heads_backward: null input");
+    int err = 0;
+    HeadsIO io{};
+    io.theta = theta; io.feat = feat; io.n = n; io.d_albedo = d_albedo; io.d_rough = d_rough; io.d_theta = d_theta;
+    const int held = n < HEADS_CHUNK ? n : HEADS_CHUNK;
+    io.w16 = c->buf<char>("heads_w16", HEADS_W16_BYTES, &err);
+    io.amax = c->buf<unsigned>("heads_amax", 2, &err);
+    io.tape = c->buf<char>("heads_tape", (size_t)((held + 63) / 64) * HEADS_TAPE_BYTES_PER_TILE, &err);
+    io.slabs = c->buf<float>("heads_slabs", (size_t)heads_grid(n) * HEADS_PARAMS, &err);
+    if (err) return 1;
+    launch_heads_backward(io, c->cfg, (hipStream_t)stream);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_bigpose_features(ra_ctx* c, const float* bpts, int n, float* feat, void* stream) {
+    if (check_ready(c, "ra_bigpose_features")) return 1;
+    RA_CHECK(c->cfg.relight, "ra_bigpose_features: needs a relight ctx with weights");
+    RA_CHECK(n >= 0, "ra_bigpose_features: bad sizes");
+    if (n == 0) return 0;
+    RA_CHECK(bpts && feat, "ra_bigpose_features: null input");
+    return ra_debug_mlp(c, bpts, n, nullptr, nullptr, feat, stream);
+}
+
 int ra_reshade_ground(ra_ctx* c, const float* ray_d, const float* albedo_map, const float* lvis, const float* ldot, int P,
                       const float* probes, int n_probes, int ph, int pw, const float* images, int ih, int iw, int attach_envmap,
                       float* rgb, float* albedo, float* shade, float* spec, void* stream) {

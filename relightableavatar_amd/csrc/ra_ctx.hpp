@@ -72,6 +72,7 @@ struct ra_ctx {
     bool have_cfg = false, have_weights = false, have_frame = false;
     bool k3cc_ok = true;        // K3CC's self-test against K3C at ra_finalize_weights (bit for bit); false -> launches of <= 8 Ki points use K3C's 4-wave tiles
     std::map<std::string, std::vector<float>> state_dict;
+    std::vector<float> heads_theta;   // ra_heads_get_params: the material heads of state_dict in the flat layout (staging for the async copy)
     HostNets host;
     // device copies
     DevBuf sarena, sarena_pairs, sarena_c, fwd_arena, bwd_arena, shead_row, barena, cond_r0, cond_r4, cond_c3, b_r0, b_r4, b_c3, light_xyz, light_area, light_sharp, light_dir;

@@ -179,6 +179,27 @@ int shade_bwd_grid(int P);
 int shade_bwd_probes_per_launch(int ph, int pw);          // 0: one probe's tile does not fit the LDS budget
 void launch_shade_bwd(const ShadeBwd& a, const ra_config& cfg, hipStream_t s);
 
+// the material heads on cached features, forward and weight gradient (ra_heads.hip); theta / d_theta: the flat layout of ra_heads_param_count
+constexpr int HEADS_PARAMS = 99332;
+constexpr int HEADS_MAX_GRID = 128;              // workgroups (= partial slabs of HEADS_PARAMS floats) at most; the grid depends on n alone
+constexpr int HEADS_CHUNK = 32768;               // points the tape holds (a multiple of the 64-point tile); longer calls run in chunks
+constexpr size_t HEADS_TAPE_BYTES_PER_TILE = 163840;      // f16 activations and scaled deltas of a 64-point tile, both heads
+constexpr size_t HEADS_W16_BYTES = 2 * 66048 * 2;         // the f16 images of the weights
+struct HeadsIO {
+    const float *theta, *feat;                            // HEADS_PARAMS; n x 256
+    int n;
+    float *albedo, *rough;                                // forward: n x 3, n (nullable)
+    const float *d_albedo, *d_rough;                      // backward: n x 3, n (nullable: that head's slice of d_theta is zeroed)
+    float* d_theta;                                       // backward: HEADS_PARAMS
+    void* w16;                                            // scratch: HEADS_W16_BYTES
+    unsigned* amax;                                       // scratch (backward): 2
+    void* tape;                                           // scratch (backward): HEADS_TAPE_BYTES_PER_TILE per tile of min(n, HEADS_CHUNK) points
+    float* slabs;                                         // scratch (backward): heads_grid(n) x HEADS_PARAMS
+};
+int heads_grid(int n);
+void launch_heads_forward(const HeadsIO& io, const ra_config& cfg, hipStream_t s);
+void launch_heads_backward(const HeadsIO& io, const ra_config& cfg, hipStream_t s);
+
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot
 void launch_scatter_maps(const int* hit_idx, const int* hit_count, int P, int premultiply, const float* acc_full,

@@ -334,6 +334,70 @@ class Engine:
                                            _ptr(d_rgb), _ptr(d_alb), _ptr(d_rgh), _ptr(d_prb), self.stream), 'ra_reshade_backward')
         return d_alb, d_rgh, d_prb
 
+    # ------------------------------------------------------------------ material heads on cached features (ra_heads.hip)
+    HEADS_KEYS = tuple(f'{net}.linears.{l}.{kind}' for net in ('albedo_network', 'roughness_network') for l in range(3) for kind in ('weight', 'bias'))
+
+    def _heads_check(self):
+        w, dp = int(self.cfg.get('relight_network_width', 128)), int(self.cfg.get('relight_network_depth', 2))
+        if (w, dp) != (128, 2):
+            raise _lib.RaError(f'the material-head kernels are compiled for relight_network_width 128 and relight_network_depth 2, not {w} / {dp}')
+
+    def heads_param_count(self) -> int:
+        return int(self.lib.ra_heads_param_count(self.ctx))
+
+    def heads_params(self) -> torch.Tensor:
+        """the two material heads as loaded (load_state_dict) in the flat layout of include/relightableavatar.h: HEADS_KEYS in order"""
+        self._heads_check()
+        theta = torch.empty(self.heads_param_count(), device=self.device)
+        check(self.lib.ra_heads_get_params(self.ctx, _ptr(theta), self.stream), 'ra_heads_get_params')
+        return theta
+
+    def heads_state_dict(self, theta) -> dict:
+        """theta split into the twelve state_dict keys (views of a host copy)"""
+        shapes = [(128, 256), (128,), (128, 128), (128,), (3, 128), (3,), (128, 256), (128,), (128, 128), (128,), (1, 128), (1,)]
+        t = theta.detach().to('cpu', torch.float32).reshape(-1)
+        assert t.numel() == sum(int(torch.Size(sh).numel()) for sh in shapes)
+        out, o = {}, 0
+        for k, sh in zip(self.HEADS_KEYS, shapes):
+            n = int(torch.Size(sh).numel())
+            out[k] = t[o:o + n].reshape(sh).clone()
+            o += n
+        return out
+
+    def heads_forward(self, theta, feat):
+        """theta (99332,), feat (n,256) -> albedo (n,3), roughness (n,)"""
+        self._heads_check()
+        d = self.device
+        theta, feat = _f32(theta.reshape(-1), d), _f32(feat.reshape(-1, 256), d)
+        assert theta.numel() == self.heads_param_count()
+        n = feat.shape[0]
+        albedo, rough = torch.empty(n, 3, device=d), torch.empty(n, device=d)
+        check(self.lib.ra_heads_forward(self.ctx, _ptr(theta), _ptr(feat), n, _ptr(albedo), _ptr(rough), self.stream), 'ra_heads_forward')
+        return albedo, rough
+
+    def heads_backward(self, theta, feat, d_albedo, d_rough):
+        """d_albedo (n,3) / d_rough (n,) (either may be None: that head's slice is zero) -> d_theta (99332,)"""
+        self._heads_check()
+        d = self.device
+        theta, feat = _f32(theta.reshape(-1), d), _f32(feat.reshape(-1, 256), d)
+        assert theta.numel() == self.heads_param_count()
+        n = feat.shape[0]
+        d_albedo = None if d_albedo is None else _f32(d_albedo.reshape(n, 3), d)
+        d_rough = None if d_rough is None else _f32(d_rough.reshape(n), d)
+        d_theta = torch.zeros_like(theta)      # zeros, not empty: a call with n == 0 writes nothing, and the gradient of an empty sum is 0
+        check(self.lib.ra_heads_backward(self.ctx, _ptr(theta), _ptr(feat), n, _ptr(d_albedo), _ptr(d_rough), _ptr(d_theta), self.stream),
+              'ra_heads_backward')
+        return d_theta
+
+    def bigpose_features(self, bpts):
+        """big-pose points (n,3) of the current frame (raw[:, 3:6]) -> the 256 features the heads see inside the renderer (f16 values)"""
+        d = self.device
+        bpts = _f32(bpts.reshape(-1, 3), d)
+        n = bpts.shape[0]
+        feat = torch.empty(n, 256, device=d)
+        check(self.lib.ra_bigpose_features(self.ctx, _ptr(bpts), n, _ptr(feat), self.stream), 'ra_bigpose_features')
+        return feat
+
     # ------------------------------------------------------------------ measurement
     def counters(self) -> dotdict:
         c = ra_counters()

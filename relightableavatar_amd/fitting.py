@@ -2,12 +2,16 @@
 on the cached maps of one frame.  Geometry and light visibility are frozen; the image loss reaches the probe, the albedo and the
 roughness through the shading sum alone.  PyTorch is plumbing here (parameters, Adam, the loss); the hot path is the two C calls
 behind relight_utils.reshade: ra_reshade and ra_reshade_backward.
+
+fit_heads trains what the reference's relighting stage trains — the weights of the two material networks (relight_network.py:45-47) and
+the probe — on cached surface features of one or more traced frames: relight_utils.material_heads (ra_heads_forward / ra_heads_backward)
+in front of the same re-shade.
 """
 import torch
 import torch.nn.functional as F
 
 from .base_utils import dotdict
-from .relight_utils import reshade
+from .relight_utils import material_heads, reshade
 
 
 def _inv_softplus(y):
@@ -94,3 +98,116 @@ def fit_relight(eng, maps, target_rgb, *, mask=None, steps, lr, fit_probe=True, 
             albedo, rough = albedo_full, rough_full
     return dotdict(probe=probe.detach().contiguous(), albedo_map=albedo.detach(), roughness_map=rough.detach(),
                    loss=[float(x) for x in torch.stack(history).cpu()])
+
+
+def _frame_cache(eng, cfg, batch, maps, target_rgb, mask, premultiplied):
+    """what a frame contributes to every step of fit_heads: features of the surface samples of the pixels that count, their constant
+    compositing weights, the cached shading maps and the target"""
+    dev = eng.device
+    f = lambda t, *s: t.detach().to(dev, torch.float32).reshape(*s).contiguous()
+    eng.set_frame(batch)
+    acc = f(maps.acc_map, -1)
+    P, S = acc.shape[0], int(cfg.n_samples)
+    hit = acc > 0
+    raw = f(maps['raw'], -1, S, 17)                       # per hit pixel in ascending ray order: cpts, bpts, resd, albedo, rough, norm, occ
+    if raw.shape[0] != int(hit.sum()):
+        raise ValueError('fit_heads: maps.raw does not match maps.acc_map (render the frame with cfg.ret_raw)')
+    keep = hit if mask is None else hit & mask.to(dev).reshape(P).bool()
+    raw = raw[keep[hit]]
+    occ = raw[..., 16]
+    # volume_rendering (net_utils.py:970-999) on the samples' occupancies, divided by the accumulated weight (sphere_tracing_renderer.py:
+    # render_human): constants of the fit, geometry is frozen
+    trans = torch.cumprod(torch.cat([torch.ones_like(occ[:, :1]), 1.0 - occ + 1e-8], dim=-1), dim=-1)[:, :-1]
+    w = occ * trans
+    o = w.sum(-1)
+    c = dotdict()
+    c.w = (w / (o[:, None] + 1e-8)).contiguous()
+    c.bg = ((1.0 - o) * cfg.bg_brightness / (o + 1e-8)).contiguous()
+    c.feat = eng.bigpose_features(raw[..., 3:6].reshape(-1, 3))
+    c.scale = acc[keep].contiguous() if premultiplied else torch.ones_like(acc[keep])      # alpha_output_: the maps are premultiplied by acc
+    c.ray_o, c.surf, c.norm = (f(t, P, 3)[keep].contiguous() for t in (maps.ray_o, maps.surf_map, maps.norm_map))
+    c.lvis, c.ldot = (f(t, P, -1)[keep].contiguous() for t in (maps.lvis_map, maps.ldot_map))
+    c.target = f(target_rgb, P, 3)[keep].contiguous()
+    c.S = S
+    return c
+
+
+def composite_heads(cfg, c, albedo_s, rough_s):
+    """per-sample head outputs (n_pixels * S, 3), (n_pixels * S,) -> albedo_map (n_pixels, 3), roughness_map (n_pixels,) as render_human
+    composites them: volume-rendering weights over the accumulated weight, clipped to [bias, bias + slope], albedo times
+    albedo_multiplier — and times acc where the renderer premultiplies its maps"""
+    n = c.w.shape[0]
+    a = (c.w[..., None] * albedo_s.reshape(n, c.S, 3)).sum(1) + c.bg[:, None]
+    r = (c.w * rough_s.reshape(n, c.S)).sum(1) + c.bg
+    a = a.clamp(cfg.albedo_bias, cfg.albedo_bias + cfg.albedo_slope)
+    r = r.clamp(cfg.roughness_bias, cfg.roughness_bias + cfg.roughness_slope)
+    if cfg.albedo_multiplier > 0:
+        a = a * cfg.albedo_multiplier
+    return a * c.scale[:, None], r * c.scale
+
+
+def heads_loss(eng, cache, theta, probe, heads=material_heads):
+    """the loss of fit_heads: the image MSE of every cached frame (_frame_cache) under `probe`, summed; heads(eng, theta, feat) ->
+    albedo, roughness per sample (tools/bench_heads.py swaps in a torch evaluation to time against)"""
+    total = 0.0
+    for c in cache:
+        albedo, rough = composite_heads(eng.cfg, c, *heads(eng, theta, c.feat))
+        rgb = reshade(eng, c.ray_o, c.surf, c.norm, albedo, rough, c.lvis, c.ldot, probe[None])[0]
+        total = total + F.mse_loss(rgb, c.target)
+    return total
+
+
+def fit_heads(net_or_eng, frames, *, steps, lr, fit_probe=True, probe_init=None, generator=None, theta_init=None):
+    """Fit the weights of albedo_network and roughness_network (and the probe) to photographs of traced frames: the relighting stage of
+    the reference (relight_trainer.py:113-118) with geometry, surface features and light visibility cached per frame.
+
+    net_or_eng: a relight Network on the GPU, or its Engine.  frames: a list of (batch, maps, target_rgb, mask): maps is what the
+    sphere-tracing / novel-light renderer returned for the batch with cfg.ret_raw and cfg.vis_novel_light (acc_map, ray_o, surf_map,
+    norm_map, lvis_map, ldot_map, raw); target_rgb (P,3) tone-mapped like the renderer's rgb_map; mask (P,) bool or None.  The pixels that
+    count are the hit pixels (acc > 0) inside the mask.
+    Per frame, once: set the frame, read the surface samples' big-pose points and occupancies from maps.raw, compute their features
+    (Engine.bigpose_features) and the constant compositing weights.  Per step and frame: material_heads -> composite over the n_samples
+    surface samples exactly as render_human does (composite_heads) -> reshade -> MSE over the pixels that count; the losses of the frames
+    are summed.  One Adam over theta (Engine.heads_params' flat layout; theta_init or the loaded weights) and — with fit_probe — the
+    probe parameter (probe = softplus(param), relight_network.py:86-89; started at probe_init (h,w,3) > 0 if given, else at the
+    network's own global_env_map_, else as relight_network.py:63-66 initialises it).  A probe that is not fitted is probe_init or the
+    network's.
+    Out of scope: the trainer's jitter-smoothness and entropy regularisers (relight_trainer.py:80-112) — the image loss alone.
+    Returns dotdict(state_dict: the twelve head keys (+ 'global_env_map_' when the probe was fitted) on the host, for
+    net.load_state_dict(..., strict=False); theta; probe (h,w,3); loss: `steps + 1` floats, before every step and after the last)."""
+    net = None if hasattr(net_or_eng, 'heads_params') else net_or_eng
+    eng = net_or_eng if net is None else net.engine()
+    cfg, dev = eng.cfg, eng.device
+    premultiplied = not bool(cfg.get('vis_ground_shading', False))
+    with torch.no_grad():
+        cache = [_frame_cache(eng, cfg, b, m, t, k, premultiplied) for b, m, t, k in frames]
+        theta = (eng.heads_params() if theta_init is None else theta_init.detach().to(dev, torch.float32).reshape(-1)).clone()
+        own = getattr(net, 'global_env_map_', None) if net is not None else None
+        if probe_init is not None:
+            p_param = _inv_softplus(probe_init.detach().to(dev, torch.float32).reshape(*probe_init.shape[-3:]).clamp_min(1e-6))
+        elif own is not None:
+            p_param = own.detach().to(dev, torch.float32).clone()
+        elif fit_probe:
+            p_param = init_probe_param(cfg, None, None, generator).to(dev)
+        else:
+            raise ValueError('fit_heads: a probe that is not fitted must be given (probe_init, or a network that carries one)')
+    theta.requires_grad_(True)
+    p_param.requires_grad_(bool(fit_probe))
+    opt = torch.optim.Adam([theta] + ([p_param] if fit_probe else []), lr=lr)
+
+    loss_fn = lambda: heads_loss(eng, cache, theta, F.softplus(p_param.expand(*p_param.shape[:2], 3)))
+
+    history = []
+    for _ in range(steps):
+        opt.zero_grad(set_to_none=True)
+        loss = loss_fn()
+        loss.backward()
+        opt.step()
+        history.append(loss.detach())
+    with torch.no_grad():
+        history.append(loss_fn())
+        probe = F.softplus(p_param.expand(*p_param.shape[:2], 3)).detach().contiguous()
+    sd = eng.heads_state_dict(theta)
+    if fit_probe:
+        sd['global_env_map_'] = p_param.detach().cpu().clone()
+    return dotdict(state_dict=sd, theta=theta.detach(), probe=probe, loss=[float(x) for x in torch.stack(history).cpu()])

@@ -77,3 +77,29 @@ def reshade(eng, ray_o, surf, norm, albedo, rough, lvis, ldot, probes):
     Gradients reach albedo, rough and probes only — the relighting stage's (relight_trainer.py:113-118): geometry is frozen and the
     light visibility was computed without gradients.  Engine.reshade is the plain (no-autograd) call."""
     return _Reshade.apply(eng, ray_o, surf, norm, albedo, rough, lvis, ldot, probes)
+
+
+class _MaterialHeads(torch.autograd.Function):
+    """the two material heads on cached features: forward = ra_heads_forward, backward = ra_heads_backward (feat is a constant)"""
+
+    @staticmethod
+    def forward(ctx, eng, theta, feat):
+        albedo, rough = eng.heads_forward(theta, feat)
+        ctx.eng = eng
+        ctx.save_for_backward(theta, feat)
+        return albedo, rough
+
+    @staticmethod
+    def backward(ctx, d_albedo, d_rough):
+        theta, feat = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None
+        d_theta = ctx.eng.heads_backward(theta, feat, d_albedo, d_rough)
+        return None, d_theta.reshape(theta.shape).to(theta.dtype), None
+
+
+def material_heads(eng, theta, feat):
+    """Differentiable material heads (relight_network.py:45-47,91-104) on cached surface features: theta (99332,) in the flat layout of
+    Engine.heads_params, feat (n,256) -> albedo (n,3), roughness (n,).  The gradient reaches theta only; n == 0 gives a zero gradient.
+    Engine.heads_forward is the plain (no-autograd) call."""
+    return _MaterialHeads.apply(eng, theta, feat)

@@ -1,0 +1,139 @@
+"""One optimisation step of fitting.fit_heads (loss, backward) on the hit pixels of a 512 x 512 relit frame: the material heads through
+ra_heads_forward / ra_heads_backward against the same step with the heads evaluated by torch (F.linear, fp32, autograd) on the same
+device.  Appends one JSON line to profiles/heads_train.jsonl.  A record, not a gate: there is no pass threshold.
+
+    python tools/bench_heads.py [--out profiles/heads_train.jsonl] [--size 512] [--reps 20]
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_heads.py --out /dev/null --reps 5 --kernels-only      # a run of its own
+    python tools/bench_heads.py --share DIR [--out ...]      # the heads kernels' share of that trace's kernel time, appended as a line
+
+Both variants are warmed up (code objects, ctx scratch, clocks), then timed interleaved with HIP events around a whole step; the median
+and the spread are reported.  Everything but the heads is shared: the composite in torch, ra_reshade and ra_reshade_backward.
+A run without a HIP device fails: there is no CPU fallback.
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import torch
+import torch.nn.functional as F
+
+HEADS_KERNELS = ('heads_kernel', 'heads_dw_kernel', 'heads_slab_sum_kernel', 'heads_pack_kernel', 'heads_absmax_kernel')
+
+
+def median(v):
+    s = sorted(v)
+    return s[len(s) // 2]
+
+
+def torch_heads(eng, theta, feat):
+    """the two heads on the flat parameters in fp32 under autograd (what a torch port of the trainer would run)"""
+    cfg = eng.cfg
+    shapes = [(128, 256), (128,), (128, 128), (128,), (3, 128), (3,), (128, 256), (128,), (128, 128), (128,), (1, 128), (1,)]
+    t, o = [], 0
+    for sh in shapes:
+        n = int(torch.Size(sh).numel())
+        t.append(theta[o:o + n].reshape(sh))
+        o += n
+
+    def run(q, slope, bias):
+        x = feat
+        for i in range(3):
+            x = F.linear(x, q[2 * i], q[2 * i + 1])
+            if i < 2:
+                x = F.softplus(x, beta=100)
+        return slope * torch.sigmoid(x) + bias
+    return run(t[:6], cfg.albedo_slope, cfg.albedo_bias), run(t[6:], cfg.roughness_slope, cfg.roughness_bias)[:, 0]
+
+
+def share(trace_dir):
+    files = glob.glob(os.path.join(trace_dir, '**', '*kernel_stats.csv'), recursive=True)
+    if not files:      # a rocpd database (rocprofv3's default output format): summarised by tools/rocpd_stats.py
+        dbs = glob.glob(os.path.join(trace_dir, '**', '*_results.db'), recursive=True)
+        assert dbs, f'no *kernel_stats.csv and no *_results.db under {trace_dir}'
+        import rocpd_stats
+        files = [dbs[0][:-len('_results.db')] + '_kernel_stats.csv']
+        rocpd_stats.main(dbs[0], files[0])
+    total, heads, rows = 0.0, 0.0, {}
+    for row in csv.DictReader(open(files[0])):
+        ns = float(row.get('TotalDurationNs') or row.get('TotalDuration(ns)') or 0)
+        name = row.get('Name') or row.get('KernelName') or ''
+        total += ns
+        for k in HEADS_KERNELS:
+            if k in name:
+                heads += ns
+                rows[k] = rows.get(k, 0.0) + ns
+    return dict(tool='bench_heads', kind='kernel_share', trace=os.path.basename(files[0]), kernel_time_ms=round(total / 1e6, 3),
+                heads_share=round(heads / total, 4) if total else None, heads_ms={k: round(v / 1e6, 3) for k, v in rows.items()},
+                note='totals over the traced run: the frame is rendered once, then 3 warm-up steps and --reps timed ones')
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join('profiles', 'heads_train.jsonl'))
+    ap.add_argument('--size', type=int, default=512)
+    ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--kernels-only', action='store_true', help='time the kernel variant alone (for a kernel trace)')
+    ap.add_argument('--share', help='directory of a rocprofv3 --kernel-trace --stats run of this script')
+    args = ap.parse_args()
+    if args.share:
+        line = json.dumps(share(args.share))
+    else:
+        from relightableavatar_amd import fitting, synthetic
+        from relightableavatar_amd.config import make_cfg
+        from relightableavatar_amd.networks import make_network
+        from relightableavatar_amd.renderer import make_renderer
+        assert torch.cuda.is_available(), 'needs an MI355X'
+        dev = torch.device('cuda:0')
+        cfg = make_cfg('novel_light')
+        net = make_network(cfg)
+        net.load_state_dict(synthetic.make_state_dict(0, relight=True, cfg=cfg))
+        net = net.to(dev).eval()
+        batch = synthetic.to_device(synthetic.make_batch(args.size, args.size, seed=0, posed=True, n_novel_lights=1), dev)
+        maps = make_renderer(cfg, net).render(batch)['probe00']
+        eng = net.engine()
+        probe = batch.novel_lights['probe00'].probe
+        probe = (probe[0] if probe.ndim == 4 else probe).to(dev).float()
+        with torch.no_grad():
+            cache = [fitting._frame_cache(eng, cfg, batch, maps, maps.rgb_map.reshape(-1, 3) * 0.9, None, True)]
+        theta = eng.heads_params().requires_grad_(True)
+
+        def step(heads):
+            theta.grad = None
+            fitting.heads_loss(eng, cache, theta, probe, heads).backward()
+        variants = [('kernels', fitting.material_heads)] + ([] if args.kernels_only else [('torch_fp32', torch_heads)])
+        for _ in range(3):
+            for _, h in variants:
+                step(h)
+        torch.cuda.synchronize()
+        t = {k: [] for k, _ in variants}
+        for _ in range(args.reps):
+            for k, h in variants:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                step(h)
+                e1.record()
+                e1.synchronize()
+                t[k].append(e0.elapsed_time(e1))
+        r = dict(tool='bench_heads', kind='step', size=args.size, hit_pixels=int(cache[0].w.shape[0]), samples=int(cache[0].feat.shape[0]),
+                 reps=args.reps, device=torch.cuda.get_device_name(0))
+        for k, v in t.items():
+            r[k + '_step_ms'] = round(median(v), 4)
+            r[k + '_step_ms_min_max'] = [round(min(v), 4), round(max(v), 4)]
+        if 'torch_fp32' in t:
+            r['kernels_over_torch'] = round(r['kernels_step_ms'] / r['torch_fp32_step_ms'], 3)
+        r['note'] = 'one loss + backward of fit_heads without the Adam update; composite, ra_reshade and ra_reshade_backward are common to both'
+        line = json.dumps(r)
+    print(line, flush=True)
+    if args.out and args.out != '/dev/null':
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'a') as f:
+            f.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()
