@@ -317,6 +317,36 @@ int ra_heads_backward(ra_ctx* ctx, const float* theta_dev, const float* feat_dev
                       const float* d_albedo_dev, const float* d_rough_dev, float* d_theta_dev, void* stream);
 int ra_bigpose_features(ra_ctx* ctx, const float* bpts_dev, int n, float* feat_dev, void* stream);
 
+/* The regularisers of the relighting stage (relight_trainer.py:70-91): what its optimisation adds to the image loss.
+ *
+ * ra_canonical_features: the 256 features of the signed-distance network on CANONICAL points (n x 3), the input of the jitter outputs
+ *   albedo_jitter / roughness_jitter = heads(signed_distance_network.feat(cpts + noise)) (relight_network.py:107-118).  No residual
+ *   deformation in front and no pose condition: it needs the weights of a relight ctx and NO frame.  feat (n x 256) has the format of
+ *   ra_bigpose_features — the values the heads read, rounded to the ctx's operand type (ra_config.mlp_f16), stored as fp32 — and for
+ *   cpts = channels 0:3 of ra_render_out.raw (the full query's own fp32 bpts + resd) it equals ra_bigpose_features(bpts) bit for bit.
+ *   feat_dev may point into a larger buffer (the second half of a 2n x 256 buffer whose first half holds cached features: one
+ *   ra_heads_forward / ra_heads_backward call then covers both).
+ *
+ * ra_gaussian_entropy: gaussian_entropy (loss_utils.py:51-76) of x (n x 3, e.g. albedo) and its gradient under torch autograd's
+ *   conventions.  15 bins on [0, 1] (the reference's defaults, the only ones its trainer uses) are compiled in.  Per channel:
+ *   m = mean, s = unbiased VARIANCE (the reference uses it as the kernel width; kept), k_nb = exp(-0.5 ((x_n - mu_b) / s)^2) /
+ *   (s sqrt(2 pi)) / 15 with mu_b = (b + 0.5) / 15, h_b = sum_n k_nb, S = sum_b h_b, p_b = h_b / S + 1e-6, E = -sum_c sum_b p_b log p_b.
+ *   value: one device float.  d_x (n x 3, may be NULL): dE/dx times *d_value_dev, including the path through s = var(x); d_value_dev
+ *   may be NULL, which means 1.  The product with *d_value_dev is the last fp32 operation: scaling it by a power of two scales d_x bit
+ *   for bit.  x is read and d_x written in fp32, the arithmetic between is double.
+ *   Deviations from the reference, deliberate:
+ *     - a channel with S <= 1e-6, with s == 0 or with a non-finite s contributes 0 to the value and EXACTLY 0 to d_x.  The reference
+ *       takes its ones_like branch for the value there (also 0), but its autograd returns NaN gradients for a constant channel;
+ *     - n < 2 is the error "bad sizes" (the reference's variance is NaN there).
+ *   Any ctx will do (no weights are read); it provides the scratch.
+ *
+ * Both are asynchronous on stream and overwrite their outputs; a null required pointer is the error "null input";
+ * ra_canonical_features returns 0 for n == 0 and gives the error "relight ctx" for a ctx that is not a relight ctx with weights.
+ * Scratch is allocated on the first call of a size only.  No float atomics: partial sums go to one slab per workgroup and are added
+ * in slab order, the grids depend on n alone, two identical calls are bit-identical. */
+int ra_canonical_features(ra_ctx* ctx, const float* cpts_dev, int n, float* feat_dev, void* stream);
+int ra_gaussian_entropy(ra_ctx* ctx, const float* x_dev, int n, const float* d_value_dev, float* value_dev, float* d_x_dev, void* stream);
+
 /* novel_light_sphere_tracing.render_ground (:70-99): re-shade the ground layer of the main pass under n_probes probes from its
  * cached per-light visibility and cosine (ra_ground_out.lvis / .ldot of ALL frame pixels, P x 512 each): Lambert ground,
  * rgb = linear2srgb(albedo / pi * sum_l lvis ldot area L_probe(l)), shade = sum / pi, spec = shade / 20 (no shading_albedo, no

@@ -119,6 +119,8 @@ SYMBOLS = {
     'ra_heads_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ra_heads_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ra_bigpose_features': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_canonical_features': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_gaussian_entropy': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ra_k3cc_enabled': (C.c_int, [C.c_void_p]),
     'ra_begin_render': (C.c_int, [C.c_void_p]),
     'ra_debug_key_lights': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -109,6 +109,12 @@ def default_cfg() -> dotdict:
     c.tonemapping_rendering = True
     c.only_visibility = False
     c.rgb_as_albedo = False
+    # the relighting stage's loss (config.py:90,198,211-213; relight_trainer.py:70-118) — fitting.fit_heads(regularisers=True)
+    c.img_loss_weight = 1.0
+    c.albedo_sparsity = 5e-4
+    c.albedo_smooth_weight = 5e-3
+    c.roughness_smooth_weight = 5e-3
+    c.xyz_noise_std = 0.02
     # visualisation switches that change what render() returns
     c.vis_rendering_map = True
     c.vis_shading_map = False

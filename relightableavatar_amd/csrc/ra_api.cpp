@@ -1139,6 +1139,33 @@ int ra_bigpose_features(ra_ctx* c, const float* bpts, int n, float* feat, void* 
     return ra_debug_mlp(c, bpts, n, nullptr, nullptr, feat, stream);
 }
 
+// ---- the regularisers of the relighting stage (ra_k4_canon.hpp, ra_entropy.hip) -------------------
+int ra_canonical_features(ra_ctx* c, const float* cpts, int n, float* feat, void* stream) {
+    if (heads_ready(c, "ra_canonical_features")) return 1;      // weights of a relight ctx; no frame: the SDF net has no pose condition
+    RA_CHECK(n >= 0, "ra_canonical_features: bad sizes");
+    if (n == 0) return 0;
+    RA_CHECK(cpts && feat, "ra_canonical_features: null input");
+    RA_CHECK(c->host.fwd_arena.size() == (size_t)2080 * 512, "ra_canonical_features: the forward stream is not the 2080 fragments the kernel walks");
+    hipStream_t s = (hipStream_t)stream;
+    if (c->cfg.mlp_f16) launch_canonical_features_f16(c->host.geo, c->fwd_arena.p, c->barena.as<float>(), cpts, n, feat, s);
+    else launch_canonical_features_bf16(c->host.geo, c->fwd_arena.p, c->barena.as<float>(), cpts, n, feat, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_gaussian_entropy(ra_ctx* c, const float* x, int n, const float* d_value, float* value, float* d_x, void* stream) {
+    RA_CHECK(c, "ra_gaussian_entropy: null ctx");
+    RA_CHECK(x && value, "ra_gaussian_entropy: null input");
+    RA_CHECK(n >= 2, "ra_gaussian_entropy: bad sizes (the variance needs two rows)");
+    RA_HIP(hipSetDevice(c->device));
+    int err = 0;
+    double* scratch = c->buf<double>("entropy", entropy_scratch_doubles(n), &err);
+    if (err) return 1;
+    launch_gaussian_entropy(x, n, d_value, value, d_x, scratch, (hipStream_t)stream);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
 int ra_reshade_ground(ra_ctx* c, const float* ray_d, const float* albedo_map, const float* lvis, const float* ldot, int P,
                       const float* probes, int n_probes, int ph, int pw, const float* images, int ih, int iw, int attach_envmap,
                       float* rgb, float* albedo, float* shade, float* spec, void* stream) {

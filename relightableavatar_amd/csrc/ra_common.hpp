@@ -153,6 +153,10 @@ void launch_mlp_bwd_heads_f16(const MatNet& mat, const ColNet& col, const void* 
 void launch_mlp_bwd_heads_bf16(const MatNet& mat, const ColNet& col, const void* bwd_arena, const float* barena, const float* shead_row, const FrameState& fr,
                                const FullIO& io, const char* tape, hipStream_t stream);
 
+// SDF features on canonical points (ra_k4_canon.hpp): the signed-distance half of K4's forward kernel, walking fwd_arena from its 976th fragment
+void launch_canonical_features_f16(const GeoNet& net, const void* fwd_arena, const float* barena, const float* cpts, int n, float* feat, hipStream_t stream);
+void launch_canonical_features_bf16(const GeoNet& net, const void* fwd_arena, const float* barena, const float* cpts, int n, float* feat, hipStream_t stream);
+
 // --- error plumbing ---------------------------------------------------------------------------
 void ra_set_error(const std::string& msg);
 #define RA_HIP(expr)                                                                         \

@@ -200,6 +200,12 @@ int heads_grid(int n);
 void launch_heads_forward(const HeadsIO& io, const ra_config& cfg, hipStream_t s);
 void launch_heads_backward(const HeadsIO& io, const ra_config& cfg, hipStream_t s);
 
+// Gaussian-histogram entropy of an n x 3 sample and its gradient (ra_entropy.hip); scratch: entropy_scratch_doubles(n) doubles
+constexpr int ENTROPY_MAX_GRID = 256;            // workgroups (= partial slabs) at most; the grid depends on n alone
+int entropy_grid(int n);
+size_t entropy_scratch_doubles(int n);
+void launch_gaussian_entropy(const float* x, int n, const float* d_value, float* value, float* d_x, double* scratch, hipStream_t s);
+
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot
 void launch_scatter_maps(const int* hit_idx, const int* hit_count, int P, int premultiply, const float* acc_full,

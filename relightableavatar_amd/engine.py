@@ -398,6 +398,32 @@ class Engine:
         check(self.lib.ra_bigpose_features(self.ctx, _ptr(bpts), n, _ptr(feat), self.stream), 'ra_bigpose_features')
         return feat
 
+    def canonical_features(self, cpts, out=None):
+        """canonical points (n,3) (raw[:, 0:3], plus noise for the jitter regularisers) -> the 256 features of the SDF network in the
+        format of bigpose_features; needs no frame.  out: a contiguous (n,256) fp32 device tensor to fill — e.g. the second half of a
+        (2n,256) buffer whose first half holds cached features"""
+        d = self.device
+        cpts = _f32(cpts.reshape(-1, 3), d)
+        n = cpts.shape[0]
+        if out is None:
+            out = torch.empty(n, 256, device=d)
+        elif not (out.is_contiguous() and out.dtype == torch.float32 and out.device == d and tuple(out.shape) == (n, 256)):
+            raise ValueError('canonical_features: out must be a contiguous fp32 (n, 256) tensor on the engine\'s device')
+        check(self.lib.ra_canonical_features(self.ctx, _ptr(cpts), n, _ptr(out), self.stream), 'ra_canonical_features')
+        return out
+
+    def gaussian_entropy(self, x, d_value=None, want_grad=True):
+        """x (n,3) -> (value: 0-dim tensor, d_x (n,3) or None): gaussian_entropy of the reference (loss_utils.py:51-76; 15 bins on [0, 1])
+        and its gradient times d_value (a one-element device tensor; None: 1)"""
+        d = self.device
+        x = _f32(x.reshape(-1, 3), d)
+        n = x.shape[0]
+        d_value = None if d_value is None else _f32(d_value.reshape(1), d)
+        value = torch.empty((), device=d)
+        d_x = torch.empty(n, 3, device=d) if want_grad else None
+        check(self.lib.ra_gaussian_entropy(self.ctx, _ptr(x), n, _ptr(d_value), _ptr(value), _ptr(d_x), self.stream), 'ra_gaussian_entropy')
+        return value, d_x
+
     # ------------------------------------------------------------------ measurement
     def counters(self) -> dotdict:
         c = ra_counters()

@@ -5,13 +5,16 @@ behind relight_utils.reshade: ra_reshade and ra_reshade_backward.
 
 fit_heads trains what the reference's relighting stage trains — the weights of the two material networks (relight_network.py:45-47) and
 the probe — on cached surface features of one or more traced frames: relight_utils.material_heads (ra_heads_forward / ra_heads_backward)
-in front of the same re-shade.
+in front of the same re-shade.  With regularisers it minimises the trainer's loss (relight_trainer.py:70-91,113-118): the image MSE plus
+the Gaussian-histogram entropy of the per-sample and of the composited albedo (relight_utils.gaussian_entropy: ra_gaussian_entropy) and
+the L1 distance of both heads' outputs from their outputs at jittered canonical points (Engine.canonical_features:
+ra_canonical_features on cpts + noise, fresh every step).
 """
 import torch
 import torch.nn.functional as F
 
 from .base_utils import dotdict
-from .relight_utils import material_heads, reshade
+from .relight_utils import gaussian_entropy, material_heads, reshade
 
 
 def _inv_softplus(y):
@@ -123,7 +126,13 @@ def _frame_cache(eng, cfg, batch, maps, target_rgb, mask, premultiplied):
     c = dotdict()
     c.w = (w / (o[:, None] + 1e-8)).contiguous()
     c.bg = ((1.0 - o) * cfg.bg_brightness / (o + 1e-8)).contiguous()
-    c.feat = eng.bigpose_features(raw[..., 3:6].reshape(-1, 3))
+    # the features twice over: rows [0, n) the samples' own (cached), rows [n, 2n) rewritten every step with the features at the jittered
+    # canonical points (regulariser_terms) — one heads call then covers both, with no concatenation per step
+    n = raw.shape[0] * S
+    c.cpts = raw[..., 0:3].reshape(-1, 3).contiguous()     # the kernel's own fp32 bpts + resd
+    c.feat2 = torch.empty(2 * n, 256, device=dev)
+    c.feat2[:n] = eng.bigpose_features(raw[..., 3:6].reshape(-1, 3))
+    c.feat = c.feat2[:n]
     c.scale = acc[keep].contiguous() if premultiplied else torch.ones_like(acc[keep])      # alpha_output_: the maps are premultiplied by acc
     c.ray_o, c.surf, c.norm = (f(t, P, 3)[keep].contiguous() for t in (maps.ray_o, maps.surf_map, maps.norm_map))
     c.lvis, c.ldot = (f(t, P, -1)[keep].contiguous() for t in (maps.lvis_map, maps.ldot_map))
@@ -132,17 +141,21 @@ def _frame_cache(eng, cfg, batch, maps, target_rgb, mask, premultiplied):
     return c
 
 
-def composite_heads(cfg, c, albedo_s, rough_s):
+def composite_heads(cfg, c, albedo_s, rough_s, want_volume=False):
     """per-sample head outputs (n_pixels * S, 3), (n_pixels * S,) -> albedo_map (n_pixels, 3), roughness_map (n_pixels,) as render_human
     composites them: volume-rendering weights over the accumulated weight, clipped to [bias, bias + slope], albedo times
-    albedo_multiplier — and times acc where the renderer premultiplies its maps"""
+    albedo_multiplier — and times acc where the renderer premultiplies its maps.  want_volume: a third output, the clipped albedo
+    composite before albedo_multiplier and before the premultiplication: ret.volume_albedo (sphere_tracing_renderer.py:645-647)"""
     n = c.w.shape[0]
     a = (c.w[..., None] * albedo_s.reshape(n, c.S, 3)).sum(1) + c.bg[:, None]
     r = (c.w * rough_s.reshape(n, c.S)).sum(1) + c.bg
     a = a.clamp(cfg.albedo_bias, cfg.albedo_bias + cfg.albedo_slope)
     r = r.clamp(cfg.roughness_bias, cfg.roughness_bias + cfg.roughness_slope)
+    volume = a
     if cfg.albedo_multiplier > 0:
         a = a * cfg.albedo_multiplier
+    if want_volume:
+        return a * c.scale[:, None], r * c.scale, volume
     return a * c.scale[:, None], r * c.scale
 
 
@@ -157,7 +170,84 @@ def heads_loss(eng, cache, theta, probe, heads=material_heads):
     return total
 
 
-def fit_heads(net_or_eng, frames, *, steps, lr, fit_probe=True, probe_init=None, generator=None, theta_init=None):
+TERMS = ('albedo_entropy', 'volume_entropy', 'albedo_smooth', 'roughness_smooth')
+WEIGHTS = ('img_loss_weight', 'albedo_sparsity', 'albedo_smooth_weight', 'roughness_smooth_weight')
+
+
+def l1(x, y):
+    """lib/utils/loss_utils.py l1: abs().sum(-1).mean()"""
+    return (x - y).abs().sum(-1).mean()
+
+
+def regulariser_weights(cfg, regularisers):
+    """fit_heads' `regularisers` argument as a dict of the four WEIGHTS: True -> the cfg's, a dict -> its entries over the cfg's"""
+    w = {k: float(cfg[k]) for k in WEIGHTS}
+    if isinstance(regularisers, dict):
+        unknown = set(regularisers) - set(WEIGHTS)
+        if unknown:
+            raise ValueError(f'fit_heads: unknown regulariser weights {sorted(unknown)} (known: {WEIGHTS})')
+        w.update({k: float(v) for k, v in regularisers.items()})
+    elif regularisers is not True:
+        raise ValueError('fit_heads: regularisers is None, True or a dict of weights')
+    return w
+
+
+def frame_terms(eng, c, theta, noise, probe=None, grad=(True, True, True), heads=material_heads, entropy=gaussian_entropy, shade=reshade):
+    """one cached frame's terms of the trainer's loss, unweighted (relight_trainer.py:70-91,113-118): albedo_entropy (per-sample albedo),
+    volume_entropy (the composited albedo, ret.volume_albedo), albedo_smooth and roughness_smooth (l1 of the samples' outputs against
+    their outputs at cpts + noise) and — with a probe (h,w,3) — img_loss.  noise: (n_samples,3) on the device.
+    grad = (entropies, albedo_smooth, roughness_smooth): a term whose weight is zero is only reported — it is evaluated without a graph,
+    and with both smoothness terms off the differentiable heads call covers the cached features alone, exactly as without regularisers.
+    heads / entropy / shade: the three device ops (tests and tools swap in torch evaluations)."""
+    cfg, n = eng.cfg, c.cpts.shape[0]
+    with torch.no_grad():
+        eng.canonical_features(c.cpts + noise.reshape(n, 3), out=c.feat2[n:])
+    jitter_grad = grad[1] or grad[2]
+    if jitter_grad:
+        albedo2, rough2 = heads(eng, theta, c.feat2)
+        albedo_s, rough_s, albedo_j, rough_j = albedo2[:n], rough2[:n], albedo2[n:], rough2[n:]
+    else:
+        albedo_s, rough_s = heads(eng, theta, c.feat)
+        with torch.no_grad():
+            albedo_j, rough_j = heads(eng, theta.detach(), c.feat2[n:])
+    albedo, rough, volume = composite_heads(cfg, c, albedo_s, rough_s, want_volume=True)
+    out = dotdict()
+    with torch.set_grad_enabled(torch.is_grad_enabled() and grad[0]):
+        out.albedo_entropy = entropy(eng, albedo_s)
+        out.volume_entropy = entropy(eng, volume)
+    with torch.set_grad_enabled(torch.is_grad_enabled() and grad[1]):
+        out.albedo_smooth = l1(albedo_s, albedo_j)
+    with torch.set_grad_enabled(torch.is_grad_enabled() and grad[2]):
+        out.roughness_smooth = l1(rough_s[:, None], rough_j[:, None])
+    if probe is not None:
+        rgb = shade(eng, c.ray_o, c.surf, c.norm, albedo, rough, c.lvis, c.ldot, probe[None])[0]
+        out.img_loss = F.mse_loss(rgb, c.target)
+    return out
+
+
+def regulariser_terms(eng, c, theta, noise):
+    """the four unweighted regulariser terms (TERMS) of one cached frame (_frame_cache) under explicit noise (n_samples,3)"""
+    t = frame_terms(eng, c, theta, noise)
+    return dotdict({k: t[k] for k in TERMS})
+
+
+def regularised_loss(eng, cache, theta, probe, weights, noises, **ops):
+    """the trainer's loss over the cached frames, summed: img_loss_weight * mse + albedo_sparsity * (H(albedo samples) + H(volume albedo))
+    + albedo_smooth_weight * l1(albedo, albedo_jitter) + roughness_smooth_weight * l1(roughness, roughness_jitter) per frame.
+    Returns (total, dotdict of the unweighted terms summed over the frames, detached)."""
+    w = weights
+    grad = (w['albedo_sparsity'] != 0, w['albedo_smooth_weight'] != 0, w['roughness_smooth_weight'] != 0)
+    total, sums = 0.0, dotdict()
+    for c, noise in zip(cache, noises):
+        t = frame_terms(eng, c, theta, noise, probe, grad, **ops)
+        total = total + (w['img_loss_weight'] * t.img_loss + w['albedo_sparsity'] * (t.albedo_entropy + t.volume_entropy) +
+                         w['albedo_smooth_weight'] * t.albedo_smooth + w['roughness_smooth_weight'] * t.roughness_smooth)
+        for k, v in t.items():
+            sums[k] = v.detach() + (sums[k] if k in sums else 0.0)
+    return total, sums
+
+
+def fit_heads(net_or_eng, frames, *, steps, lr, fit_probe=True, probe_init=None, generator=None, theta_init=None, regularisers=None, noise_fn=None):
     """Fit the weights of albedo_network and roughness_network (and the probe) to photographs of traced frames: the relighting stage of
     the reference (relight_trainer.py:113-118) with geometry, surface features and light visibility cached per frame.
 
@@ -172,9 +262,17 @@ def fit_heads(net_or_eng, frames, *, steps, lr, fit_probe=True, probe_init=None,
     probe parameter (probe = softplus(param), relight_network.py:86-89; started at probe_init (h,w,3) > 0 if given, else at the
     network's own global_env_map_, else as relight_network.py:63-66 initialises it).  A probe that is not fitted is probe_init or the
     network's.
-    Out of scope: the trainer's jitter-smoothness and entropy regularisers (relight_trainer.py:80-112) — the image loss alone.
+    regularisers: None -> the image MSE alone (no regulariser call is made).  True, or a dict of weights over the cfg's (img_loss_weight,
+    albedo_sparsity, albedo_smooth_weight, roughness_smooth_weight) -> the trainer's loss (relight_trainer.py:70-91): regularised_loss.
+    The jitter outputs are the heads on the SDF features at cpts + noise (relight_network.py:107-118); noise_fn(step, frame, n) -> (n,3)
+    on the device supplies the noise, by default torch.normal(0, cfg.xyz_noise_std) drawn on the device (seeded from `generator`), fresh per
+    step and per frame.  A term whose weight is 0 is reported but takes no part in the backward pass.
+    Still out of scope: the trainer's light-position noise (light_xyz_noise_std: the light visibility is cached) and the training-mode
+    acc (sphere_tracing_renderer.py:593-598: the geometry is frozen); the normal / visibility smoothness terms (:93-111) belong to
+    outputs the relighting stage does not train here.
     Returns dotdict(state_dict: the twelve head keys (+ 'global_env_map_' when the probe was fitted) on the host, for
-    net.load_state_dict(..., strict=False); theta; probe (h,w,3); loss: `steps + 1` floats, before every step and after the last)."""
+    net.load_state_dict(..., strict=False); theta; probe (h,w,3); loss: `steps + 1` floats, before every step and after the last; with
+    regularisers also terms: per name (img_loss and TERMS, unweighted, summed over the frames) a list like loss)."""
     net = None if hasattr(net_or_eng, 'heads_params') else net_or_eng
     eng = net_or_eng if net is None else net.engine()
     cfg, dev = eng.cfg, eng.device
@@ -195,19 +293,37 @@ def fit_heads(net_or_eng, frames, *, steps, lr, fit_probe=True, probe_init=None,
     p_param.requires_grad_(bool(fit_probe))
     opt = torch.optim.Adam([theta] + ([p_param] if fit_probe else []), lr=lr)
 
-    loss_fn = lambda: heads_loss(eng, cache, theta, F.softplus(p_param.expand(*p_param.shape[:2], 3)))
+    current_probe = lambda: F.softplus(p_param.expand(*p_param.shape[:2], 3))
+    history, terms = [], []
+    if regularisers is None:
+        loss_fn = lambda step: heads_loss(eng, cache, theta, current_probe())
+    else:
+        weights = regulariser_weights(cfg, regularisers)
+        if noise_fn is None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(torch.randint(2 ** 62, (1,), generator=generator)))
+            std = float(cfg.xyz_noise_std)
+            noise_fn = lambda step, frame, n: torch.normal(0.0, std, (n, 3), generator=gen, device=dev)
 
-    history = []
-    for _ in range(steps):
+        def loss_fn(step):
+            noises = [noise_fn(step, i, c.cpts.shape[0]).to(dev, torch.float32) for i, c in enumerate(cache)]
+            total, t = regularised_loss(eng, cache, theta, current_probe(), weights, noises)
+            terms.append(t)
+            return total
+
+    for step in range(steps):
         opt.zero_grad(set_to_none=True)
-        loss = loss_fn()
+        loss = loss_fn(step)
         loss.backward()
         opt.step()
         history.append(loss.detach())
     with torch.no_grad():
-        history.append(loss_fn())
-        probe = F.softplus(p_param.expand(*p_param.shape[:2], 3)).detach().contiguous()
+        history.append(loss_fn(steps))
+        probe = current_probe().detach().contiguous()
     sd = eng.heads_state_dict(theta)
     if fit_probe:
         sd['global_env_map_'] = p_param.detach().cpu().clone()
-    return dotdict(state_dict=sd, theta=theta.detach(), probe=probe, loss=[float(x) for x in torch.stack(history).cpu()])
+    out = dotdict(state_dict=sd, theta=theta.detach(), probe=probe, loss=[float(x) for x in torch.stack(history).cpu()])
+    if regularisers is not None:
+        out.terms = dotdict({k: [float(x) for x in torch.stack([t[k] for t in terms]).cpu()] for k in ('img_loss',) + TERMS})
+    return out

@@ -103,3 +103,26 @@ def material_heads(eng, theta, feat):
     Engine.heads_params, feat (n,256) -> albedo (n,3), roughness (n,).  The gradient reaches theta only; n == 0 gives a zero gradient.
     Engine.heads_forward is the plain (no-autograd) call."""
     return _MaterialHeads.apply(eng, theta, feat)
+
+
+class _GaussianEntropy(torch.autograd.Function):
+    """forward = ra_gaussian_entropy with the gradient kept; backward scales it by the incoming scalar"""
+
+    @staticmethod
+    def forward(ctx, eng, x):
+        value, d_x = eng.gaussian_entropy(x, want_grad=True)
+        ctx.save_for_backward(d_x)
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
+        return value
+
+    @staticmethod
+    def backward(ctx, d_value):
+        d_x, = ctx.saved_tensors
+        return None, (d_x * d_value).reshape(ctx.x_shape).to(ctx.x_dtype)
+
+
+def gaussian_entropy(eng, x):
+    """Differentiable Gaussian-histogram entropy of x (..., 3) (loss_utils.py:51-76, the albedo sparsity term of relight_trainer.py:70-81):
+    a 0-dim tensor.  A constant channel contributes 0 and a zero gradient (the reference's autograd returns NaN there).
+    Engine.gaussian_entropy is the plain (no-autograd) call."""
+    return _GaussianEntropy.apply(eng, x)

@@ -5,6 +5,11 @@ device.  Appends one JSON line to profiles/heads_train.jsonl.  A record, not a g
     python tools/bench_heads.py [--out profiles/heads_train.jsonl] [--size 512] [--reps 20]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_heads.py --out /dev/null --reps 5 --kernels-only      # a run of its own
     python tools/bench_heads.py --share DIR [--out ...]      # the heads kernels' share of that trace's kernel time, appended as a line
+    python tools/bench_heads.py --regularisers [--out profiles/relight_reg.jsonl]      # the regularised step (fit_heads(regularisers=True))
+
+--regularisers times, on the same frame: the step without regularisers (the figure above, `kernels`), the step of the trainer's loss with
+ra_canonical_features / ra_gaussian_entropy, and that step with the two entropy terms evaluated by torch (the reference's formulas under
+autograd on the same device tensors); and ra_canonical_features against ra_bigpose_features on the frame's samples.
 
 Both variants are warmed up (code objects, ctx scratch, clocks), then timed interleaved with HIP events around a whole step; the median
 and the spread are reported.  Everything but the heads is shared: the composite in torch, ra_reshade and ra_reshade_backward.
@@ -50,6 +55,73 @@ def torch_heads(eng, theta, feat):
     return run(t[:6], cfg.albedo_slope, cfg.albedo_bias), run(t[6:], cfg.roughness_slope, cfg.roughness_bias)[:, 0]
 
 
+def torch_entropy(eng, x, bins=15):
+    """lib/utils/loss_utils.py:51-76 as a torch port would run it (fp32 autograd on the device)"""
+    x = x.reshape(-1, 3)
+    sigma = x.var(dim=0)
+    centers = (torch.arange(bins, device=x.device, dtype=x.dtype) + 0.5) / bins
+    k = (-0.5 * ((x[None] - centers[:, None, None]) / sigma).pow(2)).exp() / (sigma * 2.5066282746310002) / bins
+    h = k.sum(dim=1)
+    e = 0
+    for i in range(3):
+        hi = h[:, i]
+        hi = hi / hi.sum() + 1e-6 if hi.sum() > 1e-6 else torch.ones_like(hi)
+        e = e + torch.sum(-hi * torch.log(hi))
+    return e
+
+
+def timed(variants, reps, warm=3):
+    """{name: [ms]}: the variants warmed up, then timed interleaved with HIP events around a whole call"""
+    for _ in range(warm):
+        for _, f in variants:
+            f()
+    torch.cuda.synchronize()
+    t = {k: [] for k, _ in variants}
+    for _ in range(reps):
+        for k, f in variants:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            t[k].append(e0.elapsed_time(e1))
+    return t
+
+
+def regularised_leg(args, eng, cfg, cache, theta, probe, fitting):
+    dev = eng.device
+    c = cache[0]
+    n = c.cpts.shape[0]
+    weights = fitting.regulariser_weights(cfg, True)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    noise = lambda: [torch.normal(0.0, float(cfg.xyz_noise_std), (n, 3), generator=gen, device=dev)]
+
+    def step(**ops):
+        theta.grad = None
+        fitting.regularised_loss(eng, cache, theta, probe, weights, noise(), **ops)[0].backward()
+
+    def plain():
+        theta.grad = None
+        fitting.heads_loss(eng, cache, theta, probe).backward()
+    t = timed([('plain', plain)], args.reps)          # on its own, as the default leg times it: the figure to hold against the parent commit's
+    t.update(timed([('regularised', step), ('regularised_torch_entropy', lambda: step(entropy=torch_entropy))], args.reps))
+    bpts, cpts, out = torch.rand(n, 3, device=dev) * 0.2 + 0.3, c.cpts, torch.empty(n, 256, device=dev)
+    t.update(timed([('bigpose_features', lambda: eng.bigpose_features(bpts)), ('canonical_features', lambda: eng.canonical_features(cpts, out=out)),
+                    ('gaussian_entropy', lambda: eng.gaussian_entropy(cpts))], args.reps))
+    r = dict(tool='bench_heads', kind='regularised_step', size=args.size, hit_pixels=int(c.w.shape[0]), samples=n, reps=args.reps,
+             device=torch.cuda.get_device_name(0), weights=weights)
+    for k, v in t.items():
+        r[k + '_ms'] = round(median(v), 4)
+        r[k + '_ms_min_max'] = [round(min(v), 4), round(max(v), 4)]
+    r['regularised_over_plain'] = round(r['regularised_ms'] / r['plain_ms'], 3)
+    r['canonical_over_bigpose'] = round(r['canonical_features_ms'] / r['bigpose_features_ms'], 3)
+    r['note'] = ('one loss + backward of fit_heads without the Adam update; plain: the image loss alone; regularised: the trainer\'s loss with fresh '
+                 'device noise per step; *_torch_entropy: the two entropy terms by torch autograd instead of ra_gaussian_entropy; the three last '
+                 'figures are single calls on the frame\'s samples (host launch overhead included)')
+    return r
+
+
 def share(trace_dir):
     files = glob.glob(os.path.join(trace_dir, '**', '*kernel_stats.csv'), recursive=True)
     if not files:      # a rocpd database (rocprofv3's default output format): summarised by tools/rocpd_stats.py
@@ -79,7 +151,10 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--kernels-only', action='store_true', help='time the kernel variant alone (for a kernel trace)')
     ap.add_argument('--share', help='directory of a rocprofv3 --kernel-trace --stats run of this script')
+    ap.add_argument('--regularisers', action='store_true', help='time the regularised step (default --out profiles/relight_reg.jsonl)')
     args = ap.parse_args()
+    if args.regularisers and args.out == os.path.join('profiles', 'heads_train.jsonl'):
+        args.out = os.path.join('profiles', 'relight_reg.jsonl')
     if args.share:
         line = json.dumps(share(args.share))
     else:
@@ -101,6 +176,14 @@ def main():
         with torch.no_grad():
             cache = [fitting._frame_cache(eng, cfg, batch, maps, maps.rgb_map.reshape(-1, 3) * 0.9, None, True)]
         theta = eng.heads_params().requires_grad_(True)
+        if args.regularisers:
+            line = json.dumps(regularised_leg(args, eng, cfg, cache, theta, probe, fitting))
+            print(line, flush=True)
+            if args.out and args.out != '/dev/null':
+                os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+                with open(args.out, 'a') as f:
+                    f.write(line + '\n')
+            return
 
         def step(heads):
             theta.grad = None
