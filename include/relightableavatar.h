@@ -254,6 +254,34 @@ int ra_begin_render(ra_ctx* ctx);
  * call before), and with n = 0 after them (back to per-call key lights).  No counterpart in the reference, whose arithmetic is fp32 throughout. */
 int ra_set_key_probes(ra_ctx* ctx, const float* probes_dev, int n, int probe_h, int probe_w, int accumulate, void* stream);
 
+/* The positions of the ctx's lights, moved by the caller: the reference's relight network returns light_xyz_ + randn * cfg.light_xyz_noise_std
+ * in training mode (relight_network.py:79-84; one draw per render call, sphere_tracing_renderer.py:1029), and that draw feeds the
+ * shadow-ray directions (normalize(xyz), :285), the cosine (:292) and surf2light of the probe lookup and the BRDF (:715-728).
+ * xyz_dev: n_lights x 3 fp32 (device); NULL restores the loaded light_xyz_.  Stream-ordered: the positions are copied into the ctx's own
+ * buffer on `stream` and the unit directions recomputed behind the copy; the caller's buffer is read on the stream and never kept.
+ * light_area and light_sharp do not move (the reference jitters positions only).  From here on EVERY consumer of the ctx follows the new
+ * positions until they are set again: the visibility stage of ra_render_sphere_chunk / ra_render_ground_chunk and ra_light_visibility,
+ * the key-light derivation, ra_reshade, ra_reshade_backward, ra_reshade_ground, ra_debug_lvis.  Key-light flags named through
+ * ra_set_key_probes were derived from the old directions: the call DROPS them, exactly as ra_set_key_probes(n = 0) does (name them again
+ * after the move if the frame needs them).  ra_finalize_weights restores the loaded positions.  Errors: a ctx without finalised relight
+ * weights, or without a light set. */
+int ra_set_light_xyz(ra_ctx* ctx, const float* xyz_dev, void* stream);
+
+/* light_visibility (sphere_tracing_renderer.py:265-344) for given surface points of the CURRENT frame, exactly as ra_render_sphere_chunk
+ * runs it (the same stage, fed the caller's list of points instead of a chunk's hit slots), under the ctx's current light positions
+ * (ra_set_light_xyz).  surf, norm: n x 3; acc: n — e.g. a rendered frame's surf / norm / acc maps; bbox_host6: the shadow rays' box
+ * (batch.wbounds as the frame's render left it).  Of `params` it reads shadow, shadow_near_offset, no_visibility and local_visibility
+ * and nothing else.  rows_dev: NULL -> all n points, outputs n x n_lights; else n_rows DISTINCT int32 indices into the n points in any
+ * order: only those are traced and the outputs are compact n_rows x n_lights, row k belonging to point rows_dev[k] (bit-identical to
+ * that row of the full call).  probe_dev (probe_h x probe_w x 3): the key lights (ra_config.key_light_share) are derived from it, as
+ * ra_render_sphere_chunk derives them from the probe it shades with; NULL: every ray runs in the plain tier, unless ra_set_key_probes
+ * named the key lights.  lvis, ldot: pixel-major, the layout ra_reshade reads.  Asynchronous on stream; n == 0 or n_rows == 0 returns 0
+ * and writes nothing.  The call takes no launch-variant hint slot and does not renumber the render calls' hints: a render after it runs
+ * the kernels it would have run.  With a gate (ra_set_gate) it takes its turn like the stage inside a render call. */
+int ra_light_visibility(ra_ctx* ctx, const float* surf, const float* norm, const float* acc, int n, const int* rows_dev, int n_rows,
+                        const float* bbox_host6, const float* probe_dev, int probe_h, int probe_w, const ra_sphere_params* params,
+                        float* lvis, float* ldot, void* stream);
+
 /* base_renderer.Renderer.get_pixel_value (base_renderer.py:53-113): uniform samples,
  * Network.forward per sample, alpha compositing.  near / far as the dataset delivers them: the renderer's clip
  * (base_renderer.py:120-121) is applied here (ra_config.clip_near / clip_far).  Every array of `out` is written for every ray. */

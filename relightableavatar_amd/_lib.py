@@ -127,6 +127,9 @@ SYMBOLS = {
     'ra_scatter_rows': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
     'ra_gather_rays': (C.c_int, [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 9),
     'ra_set_key_probes': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'ra_set_light_xyz': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ra_light_visibility': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_void_p,
+                                      C.c_int, C.c_int, C.POINTER(ra_sphere_params), C.c_void_p, C.c_void_p, C.c_void_p]),
     'ra_reshade_ground': (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] +
                           [C.c_void_p] * 5),
     'ra_get_counters': (C.c_int, [C.c_void_p, C.POINTER(ra_counters), C.c_void_p]),

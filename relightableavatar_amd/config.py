@@ -115,6 +115,8 @@ def default_cfg() -> dotdict:
     c.albedo_smooth_weight = 5e-3
     c.roughness_smooth_weight = 5e-3
     c.xyz_noise_std = 0.02
+    # the training-mode jitter of the light positions (config.py:50; relight_network.py:79-84) — fitting.fit_heads(light_noise=True)
+    c.light_xyz_noise_std = 1.0
     # visualisation switches that change what render() returns
     c.vis_rendering_map = True
     c.vis_shading_map = False

@@ -84,7 +84,7 @@ int ra_ctx_destroy(ra_ctx* c) {
     if (!c) return 0;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    DevBuf* bufs[] = {&c->sarena, &c->sarena_pairs, &c->sarena_c, &c->fwd_arena, &c->bwd_arena, &c->shead_row, &c->barena, &c->cond_r0, &c->cond_r4, &c->cond_c3, &c->b_r0, &c->b_r4, &c->b_c3, &c->light_xyz,
+    DevBuf* bufs[] = {&c->sarena, &c->sarena_pairs, &c->sarena_c, &c->fwd_arena, &c->bwd_arena, &c->shead_row, &c->barena, &c->cond_r0, &c->cond_r4, &c->cond_c3, &c->b_r0, &c->b_r4, &c->b_c3, &c->light_xyz, &c->light_xyz_loaded,
                       &c->light_area, &c->light_sharp, &c->light_dir, &c->fR, &c->fTh, &c->fvertA, &c->fpverts4, &c->fpnorm, &c->ftverts,
                       &c->fbias_r0, &c->fbias_r4, &c->fbias_c3, &c->fcond, &c->dcounters, &c->fbvh_pts, &c->fbvh_pairs, &c->fbvh_order,
                       &c->adj_start, &c->adj_list, &c->adj_dfaces};
@@ -214,7 +214,8 @@ int ra_finalize_weights(ra_ctx* c, void* stream) {
     }
     if (c->cfg.relight) {
         c->n_lights = (int)H.light_area.size();
-        if (upload(c->light_xyz, H.light_xyz.data(), H.light_xyz.size() * 4, s)) return 1;
+        if (upload(c->light_xyz, H.light_xyz.data(), H.light_xyz.size() * 4, s)) return 1;        // the current positions: the loaded ones again
+        if (upload(c->light_xyz_loaded, H.light_xyz.data(), H.light_xyz.size() * 4, s)) return 1;
         if (upload(c->light_area, H.light_area.data(), H.light_area.size() * 4, s)) return 1;
         if (upload(c->light_sharp, H.light_sharp.data(), H.light_sharp.size() * 4, s)) return 1;
         if (c->light_dir.ensure(H.light_xyz.size() * 4)) return 1;
@@ -1563,6 +1564,38 @@ int ra_debug_aabb(ra_ctx* c, const float* o, const float* d, int n, const float*
     return 0;
 }
 
+// light_visibility on caller-given surface points (ra_light_visibility, ra_debug_lvis): the render chunk's stage with the caller's list as
+// its hit slots.  rows == nullptr: every point is its own hit slot.  No HintScope and no zero_chunk_counters: the render calls' hints and
+// their numbering stay as they are, and the stage zeroes its ray counter itself.
+static int lvis_on_points(ra_ctx* c, const float* surf, const float* norm, const float* acc, int n, const int* rows, int n_rows, const float* bbox,
+                          const ra_trace_params& shadow, float near_offset, int no_visibility, int local_visibility, float* lvis_out,
+                          float* ldot_out, hipStream_t s) {
+    const int P = rows ? n_rows : n;
+    int err = 0;
+    int* hit_count = icnt(c, CNT_HIT);
+    const int* hit_idx = rows;
+    const float* norm_slots = norm;
+    if (rows) {      // the stage reads normals per hit slot, surf and acc per point
+        float* ns = c->buf<float>("dl_norm", (size_t)P * 3, &err);
+        if (err) return 1;
+        RA_HIP(hipMemsetD32Async((hipDeviceptr_t)hit_count, P, 1, s));
+        launch_gather_rows(rows, hit_count, P, norm, 3, ns, s);
+        norm_slots = ns;
+    } else {
+        int* iota = c->buf<int>("dl_hit", P, &err);
+        if (err) return 1;
+        launch_iota(iota, P, hit_count, s);
+        hit_idx = iota;
+    }
+    float *lvis = nullptr, *ldot = nullptr;
+    if (light_visibility_stage(c, surf, norm_slots, acc, hit_idx, hit_count, P, bbox, near_offset, shadow, no_visibility, local_visibility, &lvis, &ldot, s))
+        return 1;
+    RA_HIP(hipMemcpyAsync(lvis_out, lvis, (size_t)P * c->n_lights * 4, hipMemcpyDeviceToDevice, s));
+    RA_HIP(hipMemcpyAsync(ldot_out, ldot, (size_t)P * c->n_lights * 4, hipMemcpyDeviceToDevice, s));
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
 int ra_debug_lvis(ra_ctx* c, const float* surf, const float* norm, const float* acc, int n, const float* bbox, const ra_trace_params* shadow,
                   float near_offset, float* lvis_out, float* ldot_out, void* stream) {
     if (check_ready(c, "ra_debug_lvis")) return 1;
@@ -1570,15 +1603,35 @@ int ra_debug_lvis(ra_ctx* c, const float* surf, const float* norm, const float* 
     RA_CHECK(n >= 0 && shadow && (n == 0 || (surf && norm && acc && bbox && lvis_out && ldot_out)), "ra_debug_lvis: bad arguments");
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    int err = 0;
-    int* hit_idx = c->buf<int>("dl_hit", n, &err);
-    if (err) return 1;
-    launch_iota(hit_idx, n, icnt(c, CNT_HIT), s);          // every point is its own hit slot
-    float *lvis = nullptr, *ldot = nullptr;
     if (key_mask_from(c, nullptr, 0, 0, s)) return 1;       // no probe here: every ray in the plain tier (unless ra_set_key_probes named the key lights)
-    if (light_visibility_stage(c, surf, norm, acc, hit_idx, icnt(c, CNT_HIT), n, bbox, near_offset, *shadow, 0, 0, &lvis, &ldot, s)) return 1;
-    RA_HIP(hipMemcpyAsync(lvis_out, lvis, (size_t)n * c->n_lights * 4, hipMemcpyDeviceToDevice, s));
-    RA_HIP(hipMemcpyAsync(ldot_out, ldot, (size_t)n * c->n_lights * 4, hipMemcpyDeviceToDevice, s));
+    return lvis_on_points(c, surf, norm, acc, n, nullptr, 0, bbox, *shadow, near_offset, 0, 0, lvis_out, ldot_out, s);
+}
+
+int ra_light_visibility(ra_ctx* c, const float* surf, const float* norm, const float* acc, int n, const int* rows, int n_rows, const float* bbox,
+                        const float* probe, int ph, int pw, const ra_sphere_params* p, float* lvis_out, float* ldot_out, void* stream) {
+    if (check_ready(c, "ra_light_visibility")) return 1;
+    RA_CHECK(c->cfg.relight && c->n_lights > 0, "ra_light_visibility: needs the relight network's light set");
+    RA_CHECK(n >= 0 && p && (!rows || n_rows >= 0) && (!probe || (ph > 0 && pw > 0)), "ra_light_visibility: bad arguments");
+    const int P = rows ? n_rows : n;
+    if (n == 0 || P == 0) return 0;
+    RA_CHECK(surf && norm && acc && bbox && lvis_out && ldot_out, "ra_light_visibility: null input");
+    RA_CHECK(P <= n, "ra_light_visibility: more rows than points (rows are distinct indices into the n points)");
+    RA_CHECK((long long)P * c->n_lights < (1ll << 31), "ra_light_visibility: too many rays (points x lights must fit an int): trace the frame in row subsets");
+    hipStream_t s = (hipStream_t)stream;
+    if (key_mask_from(c, probe, ph, pw, s)) return 1;       // the key lights of the probe the caller shades with, as in a render call
+    return lvis_on_points(c, surf, norm, acc, n, rows, n_rows, bbox, p->shadow, p->shadow_near_offset, p->no_visibility, p->local_visibility,
+                          lvis_out, ldot_out, s);
+}
+
+int ra_set_light_xyz(ra_ctx* c, const float* xyz, void* stream) {
+    RA_CHECK(c && c->have_weights && c->cfg.relight, "ra_set_light_xyz: needs a relight ctx with weights");
+    RA_CHECK(c->n_lights > 0 && c->light_xyz.p && c->light_xyz_loaded.p, "ra_set_light_xyz: the ctx has no light set");
+    RA_HIP(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipMemcpyAsync(c->light_xyz.p, xyz ? (const void*)xyz : c->light_xyz_loaded.p, (size_t)c->n_lights * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    launch_light_dirs(c->light_xyz.as<float>(), c->n_lights, c->light_dir.as<float>(), s);
+    c->key_external = false;      // flags named through ra_set_key_probes belong to the old directions
+    c->key_valid = false;
     RA_HIP(hipGetLastError());
     return 0;
 }

@@ -77,6 +77,8 @@ struct ra_ctx {
     // device copies
     DevBuf sarena, sarena_pairs, sarena_c, fwd_arena, bwd_arena, shead_row, barena, cond_r0, cond_r4, cond_c3, b_r0, b_r4, b_c3, light_xyz, light_area, light_sharp, light_dir;
     int n_lights = 0;
+    // light_xyz / light_dir are the positions every consumer reads: the loaded light_xyz_ unless ra_set_light_xyz moved them
+    DevBuf light_xyz_loaded;      // light_xyz_ as loaded (ra_finalize_weights): what ra_set_light_xyz(NULL) copies back
     // the key-light tier (ra_config.key_light_share): per-light flags of the current frame's probes, on the device
     DevBuf key_mask, key_share;   // (key_share: every light's largest share of a probe's power among the frame's probes)
     bool key_valid = false;       // the flags were computed for the probes this frame is shaded with

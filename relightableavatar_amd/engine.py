@@ -3,6 +3,7 @@
 PyTorch is plumbing here: it owns device memory (torch tensors whose data_ptr() is handed to the
 library) and the stream.  All arithmetic of the render path happens in the HIP library.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -264,6 +265,50 @@ class Engine:
             pr = _f32(pr if pr.ndim == 4 else pr[None], self.device)
             self._keep.append(pr)
             check(self.lib.ra_set_key_probes(self.ctx, _ptr(pr), pr.shape[0], pr.shape[1], pr.shape[2], int(i > 0), self.stream), 'ra_set_key_probes')
+
+    # ------------------------------------------------------------------ moved lights, re-traced visibility
+    def set_light_xyz(self, xyz):
+        """move the context's lights (ra_set_light_xyz): xyz (L,3) or anything that reshapes to it — e.g. light_xyz_ plus the trainer's
+        noise (relight_network.py:79-84); None restores the loaded positions.  Every later call of this engine follows the new positions
+        (renders, light_visibility, reshade and its backward, the key lights); key lights named by set_key_probes are dropped."""
+        if xyz is not None:
+            xyz = _f32(xyz.reshape(-1, 3), self.device)
+            L = int(self.cfg.env_h * self.cfg.env_w)
+            if xyz.shape[0] != L:
+                raise ValueError(f'set_light_xyz: {xyz.shape[0]} positions for {L} lights')
+        check(self.lib.ra_set_light_xyz(self.ctx, _ptr(xyz), self.stream), 'ra_set_light_xyz')      # copied on the stream: xyz may be freed after the call
+
+    @contextlib.contextmanager
+    def light_positions(self, xyz):
+        """with eng.light_positions(xyz): ... — the lights at xyz inside the block, the loaded positions after it, also on an exception"""
+        self.set_light_xyz(xyz)
+        try:
+            yield self
+        finally:
+            self.set_light_xyz(None)
+
+    def light_visibility(self, surf, norm, acc, bbox6, probe=None, rows=None, params=None):
+        """light_visibility (sphere_tracing_renderer.py:265-344) on cached surface points of the current frame under the current light
+        positions (ra_light_visibility): surf, norm (n,3), acc (n,), bbox6 the shadow rays' box -> (lvis, ldot), each (n, L) — or, with
+        rows (distinct indices into the n points, any order; int32 on the device is passed as it is), (len(rows), L), row k belonging to
+        point rows[k].  probe (h,w,3): the key lights are derived from it as in a render call; params: sphere_params() by default."""
+        dv = self.device
+        surf, norm, acc = _f32(surf.reshape(-1, 3), dv), _f32(norm.reshape(-1, 3), dv), _f32(acc.reshape(-1), dv)
+        n = surf.shape[0]
+        if rows is not None:
+            rows = torch.as_tensor(rows).detach().to(device=dv, dtype=torch.int32).reshape(-1).contiguous()
+        m = n if rows is None else rows.shape[0]
+        L = int(self.cfg.env_h * self.cfg.env_w)
+        lvis, ldot = torch.empty(m, L, device=dv), torch.empty(m, L, device=dv)
+        if m == 0:      # nothing to trace (an empty tensor has no address to hand over)
+            return lvis, ldot
+        probe = None if probe is None else _f32(probe[0] if probe.ndim == 4 else probe, dv)
+        ph, pw = (probe.shape[0], probe.shape[1]) if probe is not None else (0, 0)
+        bb = (C.c_float * 6)(*[float(v) for v in bbox6])
+        p = self.sphere_params() if params is None else params
+        check(self.lib.ra_light_visibility(self.ctx, _ptr(surf), _ptr(norm), _ptr(acc), n, _ptr(rows), m if rows is not None else 0, bb, _ptr(probe),
+                                           ph, pw, C.byref(p), _ptr(lvis), _ptr(ldot), self.stream), 'ra_light_visibility')
+        return lvis, ldot
 
     def reshade_ground(self, ray_d, albedo_map, lvis, ldot, probes, images=None, attach_envmap=True):
         """novel_light_sphere_tracing.render_ground (:70-99) for all probes at once: probes (n,h,w,3), optional images

@@ -8,13 +8,17 @@ the probe — on cached surface features of one or more traced frames: relight_u
 in front of the same re-shade.  With regularisers it minimises the trainer's loss (relight_trainer.py:70-91,113-118): the image MSE plus
 the Gaussian-histogram entropy of the per-sample and of the composited albedo (relight_utils.gaussian_entropy: ra_gaussian_entropy) and
 the L1 distance of both heads' outputs from their outputs at jittered canonical points (Engine.canonical_features:
-ra_canonical_features on cpts + noise, fresh every step).
+ra_canonical_features on cpts + noise, fresh every step).  With light_noise it also moves the lights every step as the reference's network does
+in training mode (relight_network.py:79-84) and traces the frames' light visibility again under the moved lights
+(Engine.light_visibility: ra_set_light_xyz, ra_light_visibility), on all counted pixels or on pixels_per_step of them.
 """
+import functools
+
 import torch
 import torch.nn.functional as F
 
 from .base_utils import dotdict
-from .relight_utils import gaussian_entropy, material_heads, reshade
+from .relight_utils import gaussian_entropy, gen_light_xyz, material_heads, reshade
 
 
 def _inv_softplus(y):
@@ -103,9 +107,11 @@ def fit_relight(eng, maps, target_rgb, *, mask=None, steps, lr, fit_probe=True, 
                    loss=[float(x) for x in torch.stack(history).cpu()])
 
 
-def _frame_cache(eng, cfg, batch, maps, target_rgb, mask, premultiplied):
+def _frame_cache(eng, cfg, batch, maps, target_rgb, mask, premultiplied, retrace=False):
     """what a frame contributes to every step of fit_heads: features of the surface samples of the pixels that count, their constant
-    compositing weights, the cached shading maps and the target"""
+    compositing weights, the cached shading maps and the target.  retrace (fit_heads' light noise): instead of the cached lvis / ldot —
+    two n x 512 tables that moved lights make useless — the inputs of Engine.light_visibility: the frame's batch, the counted pixels'
+    surface points, normals and acc, and the shadow rays' box"""
     dev = eng.device
     f = lambda t, *s: t.detach().to(dev, torch.float32).reshape(*s).contiguous()
     eng.set_frame(batch)
@@ -135,9 +141,17 @@ def _frame_cache(eng, cfg, batch, maps, target_rgb, mask, premultiplied):
     c.feat = c.feat2[:n]
     c.scale = acc[keep].contiguous() if premultiplied else torch.ones_like(acc[keep])      # alpha_output_: the maps are premultiplied by acc
     c.ray_o, c.surf, c.norm = (f(t, P, 3)[keep].contiguous() for t in (maps.ray_o, maps.surf_map, maps.norm_map))
-    c.lvis, c.ldot = (f(t, P, -1)[keep].contiguous() for t in (maps.lvis_map, maps.ldot_map))
+    if retrace:
+        c.lvis = c.ldot = None
+        c.batch, c.acc = batch, acc[keep].contiguous()
+        # the stage traces from the surface point itself: the maps are premultiplied by acc (x / 1 is x: pixels with acc == 1, nearly all, are
+        # handed over bit for bit)
+        c.surf_pts, c.norm_pts = ((t / c.acc[:, None]).contiguous() for t in (c.surf, c.norm)) if premultiplied else (c.surf, c.norm)
+        c.bbox = [float(v) for v in batch.wbounds.detach().reshape(-1).cpu()]      # as the frame's render left it (grown in place, quirk 1)
+    else:
+        c.lvis, c.ldot = (f(t, P, -1)[keep].contiguous() for t in (maps.lvis_map, maps.ldot_map))
     c.target = f(target_rgb, P, 3)[keep].contiguous()
-    c.S = S
+    c.S, c.premultiplied = S, bool(premultiplied)
     return c
 
 
@@ -159,13 +173,14 @@ def composite_heads(cfg, c, albedo_s, rough_s, want_volume=False):
     return a * c.scale[:, None], r * c.scale
 
 
-def heads_loss(eng, cache, theta, probe, heads=material_heads):
+def heads_loss(eng, cache, theta, probe, heads=material_heads, shades=None):
     """the loss of fit_heads: the image MSE of every cached frame (_frame_cache) under `probe`, summed; heads(eng, theta, feat) ->
-    albedo, roughness per sample (tools/bench_heads.py swaps in a torch evaluation to time against)"""
+    albedo, roughness per sample (tools/bench_heads.py swaps in a torch evaluation to time against); shades: one re-shade op per frame
+    (step_frame's, which carries the frame's light positions) instead of relight_utils.reshade"""
     total = 0.0
-    for c in cache:
+    for i, c in enumerate(cache):
         albedo, rough = composite_heads(eng.cfg, c, *heads(eng, theta, c.feat))
-        rgb = reshade(eng, c.ray_o, c.surf, c.norm, albedo, rough, c.lvis, c.ldot, probe[None])[0]
+        rgb = (reshade if shades is None else shades[i])(eng, c.ray_o, c.surf, c.norm, albedo, rough, c.lvis, c.ldot, probe[None])[0]
         total = total + F.mse_loss(rgb, c.target)
     return total
 
@@ -231,14 +246,17 @@ def regulariser_terms(eng, c, theta, noise):
     return dotdict({k: t[k] for k in TERMS})
 
 
-def regularised_loss(eng, cache, theta, probe, weights, noises, **ops):
+def regularised_loss(eng, cache, theta, probe, weights, noises, shades=None, **ops):
     """the trainer's loss over the cached frames, summed: img_loss_weight * mse + albedo_sparsity * (H(albedo samples) + H(volume albedo))
     + albedo_smooth_weight * l1(albedo, albedo_jitter) + roughness_smooth_weight * l1(roughness, roughness_jitter) per frame.
+    shades: one re-shade op per frame (step_frame's) instead of ops['shade'] / relight_utils.reshade.
     Returns (total, dotdict of the unweighted terms summed over the frames, detached)."""
     w = weights
     grad = (w['albedo_sparsity'] != 0, w['albedo_smooth_weight'] != 0, w['roughness_smooth_weight'] != 0)
     total, sums = 0.0, dotdict()
-    for c, noise in zip(cache, noises):
+    for i, (c, noise) in enumerate(zip(cache, noises)):
+        if shades is not None:
+            ops['shade'] = shades[i]
         t = frame_terms(eng, c, theta, noise, probe, grad, **ops)
         total = total + (w['img_loss_weight'] * t.img_loss + w['albedo_sparsity'] * (t.albedo_entropy + t.volume_entropy) +
                          w['albedo_smooth_weight'] * t.albedo_smooth + w['roughness_smooth_weight'] * t.roughness_smooth)
@@ -247,7 +265,68 @@ def regularised_loss(eng, cache, theta, probe, weights, noises, **ops):
     return total, sums
 
 
-def fit_heads(net_or_eng, frames, *, steps, lr, fit_probe=True, probe_init=None, generator=None, theta_init=None, regularisers=None, noise_fn=None):
+def step_options(cfg, light_noise, light_noise_fn, pixels_per_step, pixel_fn):
+    """fit_heads' light_noise / light_noise_fn / pixels_per_step / pixel_fn arguments checked: (noisy, std of the default draw, pixels per
+    step as an int or None)"""
+    if light_noise is not None and light_noise is not True and (isinstance(light_noise, bool) or not isinstance(light_noise, (int, float))):
+        raise ValueError('fit_heads: light_noise is None, True or a std')
+    std = float(cfg.light_xyz_noise_std) if light_noise is True or light_noise is None else float(light_noise)
+    if not std >= 0.0:
+        raise ValueError('fit_heads: light_noise must be a std >= 0')
+    if light_noise_fn is not None and not callable(light_noise_fn):
+        raise ValueError('fit_heads: light_noise_fn(step, frame) -> (L, 3) must be callable')
+    if pixels_per_step is not None and (isinstance(pixels_per_step, bool) or not isinstance(pixels_per_step, int) or pixels_per_step < 1):
+        raise ValueError('fit_heads: pixels_per_step is None or a positive number of pixels')
+    if pixel_fn is not None and (pixels_per_step is None or not callable(pixel_fn)):
+        raise ValueError('fit_heads: pixel_fn(step, frame, n_pixels) chooses pixels_per_step pixels: give pixels_per_step')
+    return light_noise is not None or light_noise_fn is not None, std, pixels_per_step
+
+
+def loaded_light_xyz(net, cfg, dev):
+    """light_xyz_ (L,3) on the device: the network's buffer, or — for a bare Engine — what the network generates it from (relight_network.py)"""
+    xyz = getattr(net, 'light_xyz_', None) if net is not None else None
+    if xyz is None:
+        xyz = gen_light_xyz(cfg.env_h, cfg.env_w, cfg.env_r)[0]
+    return xyz.detach().to(dev, torch.float32).reshape(-1, 3).contiguous()
+
+
+def step_frame(eng, c, probe, rows=None, light_xyz=None):
+    """one frame of one step of fit_heads under a pixel subset and / or moved lights: (view, shade).  view: the frame's cache
+    (_frame_cache) restricted to the pixels `rows` (int64 (N,) on the device, distinct indices into the counted pixels; None: all of them)
+    — the pixels' rows of every per-pixel table and their samples' rows of every per-sample one, gathered.  light_xyz (L,3): the frame was
+    cached with retrace; its batch is set, the lights are moved for the duration of the trace, and view.lvis / view.ldot are
+    Engine.light_visibility of the rows under light_xyz with `probe` (h,w,3) as the key-light probe — times acc where the renderer
+    premultiplies its maps, as the cached maps are.  shade: relight_utils.reshade carrying light_xyz."""
+    v = c
+    if rows is not None:
+        n, S = c.w.shape[0], c.S
+        v = dotdict(c)
+        for k in ('w', 'bg', 'scale', 'ray_o', 'surf', 'norm', 'target'):
+            v[k] = c[k][rows]
+        N = rows.shape[0]
+        v.cpts = c.cpts.reshape(n, S, 3)[rows].reshape(N * S, 3)
+        v.feat2 = torch.empty(2 * N * S, 256, device=c.feat.device)
+        v.feat2[:N * S] = c.feat.reshape(n, S, 256)[rows].reshape(N * S, 256)
+        v.feat = v.feat2[:N * S]
+        if light_xyz is None:
+            v.lvis, v.ldot = c.lvis[rows], c.ldot[rows]
+    if light_xyz is None:
+        return v, reshade
+    if v is c:
+        v = dotdict(c)
+    with torch.no_grad():      # light visibility carries no gradient (sphere_tracing_renderer.py:265: under no_grad)
+        eng.set_frame(c.batch)
+        with eng.light_positions(light_xyz):
+            lvis, ldot = eng.light_visibility(c.surf_pts, c.norm_pts, c.acc, c.bbox, probe=probe.detach(),
+                                              rows=None if rows is None else rows.to(torch.int32))
+        if c.premultiplied:
+            lvis, ldot = lvis * v.scale[:, None], ldot * v.scale[:, None]
+    v.lvis, v.ldot = lvis, ldot
+    return v, functools.partial(reshade, light_xyz=light_xyz)
+
+
+def fit_heads(net_or_eng, frames, *, steps, lr, fit_probe=True, probe_init=None, generator=None, theta_init=None, regularisers=None, noise_fn=None,
+              light_noise=None, light_noise_fn=None, pixels_per_step=None, pixel_fn=None):
     """Fit the weights of albedo_network and roughness_network (and the probe) to photographs of traced frames: the relighting stage of
     the reference (relight_trainer.py:113-118) with geometry, surface features and light visibility cached per frame.
 
@@ -267,18 +346,38 @@ def fit_heads(net_or_eng, frames, *, steps, lr, fit_probe=True, probe_init=None,
     The jitter outputs are the heads on the SDF features at cpts + noise (relight_network.py:107-118); noise_fn(step, frame, n) -> (n,3)
     on the device supplies the noise, by default torch.normal(0, cfg.xyz_noise_std) drawn on the device (seeded from `generator`), fresh per
     step and per frame.  A term whose weight is 0 is reported but takes no part in the backward pass.
-    Still out of scope: the trainer's light-position noise (light_xyz_noise_std: the light visibility is cached) and the training-mode
-    acc (sphere_tracing_renderer.py:593-598: the geometry is frozen); the normal / visibility smoothness terms (:93-111) belong to
-    outputs the relighting stage does not train here.
+    light_noise: None -> the lights stay where they were loaded, the cached lvis_map / ldot_map are used and no call beyond today's is made
+    (results are bit-identical to a call without the argument).  True -> cfg.light_xyz_noise_std, or a float: that std.  The reference's
+    network returns light_xyz_ + randn * std in training mode (relight_network.py:79-84), evaluated once per render call
+    (sphere_tracing_renderer.py:1029); that draw moves the shadow rays, the cosines and the probe lookup together.  So per step and
+    frame: xyz = light_xyz_ + noise (ONE draw), the rows are chosen, Engine.light_visibility traces them again on the cached surface
+    points, normals and acc of the counted pixels with the current probe as the key-light probe, then heads -> composite ->
+    reshade(light_xyz=xyz) -> loss.  light_noise_fn(step, frame) -> (L,3) on the device supplies the noise where it must be controlled
+    (it alone switches the noise on, too); by default torch.normal(0, std, (L,3)) on the device from a generator seeded from `generator`.
+    The cached lvis / ldot tables are not kept then.  The shadow rays' box is batch.wbounds as the frame's render left it (the renderer
+    grows it in place, quirk 1): for a frame rendered as one chunk the box its cached visibility was clipped against, for a frame of
+    several chunks the LAST chunk's — wider than the box of the earlier chunks' pixels by the margin per chunk.  Frames that share a
+    batch object must have been rendered the same way.
+    pixels_per_step: None -> every counted pixel every step.  N -> every step and frame uses N of the frame's counted pixels (the
+    reference's train batch; the visibility stage of a whole frame every step is the cost of a rendered frame); a frame with fewer counts
+    whole.  pixel_fn(step, frame, n_pixels) -> int64 (N,) distinct indices below n_pixels on the device controls the choice (the indices
+    are not checked: a check would read them back every step); the default is a randperm prefix drawn on the device.  The entropy and
+    smoothness terms then run over the chosen pixels' samples, and noise_fn is asked for N * n_samples rows.  Usable without light
+    noise: the rows of the cached visibility are gathered.
+    On return and on any exception the engine's light positions are the loaded ones.
+    Still out of scope: the training-mode acc (sphere_tracing_renderer.py:593-598: the geometry is frozen); the normal / visibility
+    smoothness terms (:93-111) belong to outputs the relighting stage does not train here.
     Returns dotdict(state_dict: the twelve head keys (+ 'global_env_map_' when the probe was fitted) on the host, for
     net.load_state_dict(..., strict=False); theta; probe (h,w,3); loss: `steps + 1` floats, before every step and after the last; with
     regularisers also terms: per name (img_loss and TERMS, unweighted, summed over the frames) a list like loss)."""
     net = None if hasattr(net_or_eng, 'heads_params') else net_or_eng
+    noisy, light_std, pixels_per_step = step_options(net_or_eng.cfg, light_noise, light_noise_fn, pixels_per_step, pixel_fn)
     eng = net_or_eng if net is None else net.engine()
     cfg, dev = eng.cfg, eng.device
     premultiplied = not bool(cfg.get('vis_ground_shading', False))
+    stepwise = noisy or pixels_per_step is not None      # a frame's tables are rebuilt every step (step_frame)
     with torch.no_grad():
-        cache = [_frame_cache(eng, cfg, b, m, t, k, premultiplied) for b, m, t, k in frames]
+        cache = [_frame_cache(eng, cfg, b, m, t, k, premultiplied, **(dict(retrace=True) if noisy else {})) for b, m, t, k in frames]
         theta = (eng.heads_params() if theta_init is None else theta_init.detach().to(dev, torch.float32).reshape(-1)).clone()
         own = getattr(net, 'global_env_map_', None) if net is not None else None
         if probe_init is not None:
@@ -295,31 +394,61 @@ def fit_heads(net_or_eng, frames, *, steps, lr, fit_probe=True, probe_init=None,
 
     current_probe = lambda: F.softplus(p_param.expand(*p_param.shape[:2], 3))
     history, terms = [], []
-    if regularisers is None:
-        loss_fn = lambda step: heads_loss(eng, cache, theta, current_probe())
-    else:
+
+    def device_generator():
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(torch.randint(2 ** 62, (1,), generator=generator)))
+        return gen
+
+    if regularisers is not None:
         weights = regulariser_weights(cfg, regularisers)
         if noise_fn is None:
-            gen = torch.Generator(device=dev)
-            gen.manual_seed(int(torch.randint(2 ** 62, (1,), generator=generator)))
+            gen = device_generator()
             std = float(cfg.xyz_noise_std)
             noise_fn = lambda step, frame, n: torch.normal(0.0, std, (n, 3), generator=gen, device=dev)
+    if noisy:
+        xyz0 = loaded_light_xyz(net, cfg, dev)
+        if light_noise_fn is None:
+            light_gen = device_generator()
+            light_noise_fn = lambda step, frame: torch.normal(0.0, light_std, (xyz0.shape[0], 3), generator=light_gen, device=dev)
+    if pixels_per_step is not None and pixel_fn is None:
+        pixel_gen = device_generator()
+        pixel_fn = lambda step, frame, n: torch.randperm(n, generator=pixel_gen, device=dev)[:int(pixels_per_step)]
 
-        def loss_fn(step):
-            noises = [noise_fn(step, i, c.cpts.shape[0]).to(dev, torch.float32) for i, c in enumerate(cache)]
-            total, t = regularised_loss(eng, cache, theta, current_probe(), weights, noises)
-            terms.append(t)
-            return total
+    def step_frames(step, probe):
+        """every frame's view and re-shade op of this step: one noise draw, then one choice of rows, per frame"""
+        views, shades = [], []
+        for i, c in enumerate(cache):
+            xyz = xyz0 + light_noise_fn(step, i).to(dev, torch.float32).reshape(-1, 3) if noisy else None
+            n = c.w.shape[0]
+            rows = pixel_fn(step, i, n).to(dev, torch.int64).reshape(-1) if pixels_per_step is not None and n > int(pixels_per_step) else None
+            v, shade = step_frame(eng, c, probe, rows, xyz)
+            views.append(v), shades.append(shade)
+        return views, shades
 
-    for step in range(steps):
-        opt.zero_grad(set_to_none=True)
-        loss = loss_fn(step)
-        loss.backward()
-        opt.step()
-        history.append(loss.detach())
-    with torch.no_grad():
-        history.append(loss_fn(steps))
-        probe = current_probe().detach().contiguous()
+    def loss_fn(step):
+        probe = current_probe()
+        views, shades = step_frames(step, probe) if stepwise else (cache, None)
+        if regularisers is None:
+            return heads_loss(eng, views, theta, probe, shades=shades)
+        noises = [noise_fn(step, i, c.cpts.shape[0]).to(dev, torch.float32) for i, c in enumerate(views)]
+        total, t = regularised_loss(eng, views, theta, probe, weights, noises, shades=shades)
+        terms.append(t)
+        return total
+
+    try:
+        for step in range(steps):
+            opt.zero_grad(set_to_none=True)
+            loss = loss_fn(step)
+            loss.backward()
+            opt.step()
+            history.append(loss.detach())
+        with torch.no_grad():
+            history.append(loss_fn(steps))
+            probe = current_probe().detach().contiguous()
+    finally:
+        if noisy:
+            eng.set_light_xyz(None)
     sd = eng.heads_state_dict(theta)
     if fit_probe:
         sd['global_env_map_'] = p_param.detach().cpu().clone()

@@ -54,29 +54,47 @@ def gen_light_xyz(env_h: int, env_w: int, env_r: float):
 
 
 class _Reshade(torch.autograd.Function):
-    """rgb of Engine.reshade with its gradient: forward = ra_reshade, backward = ra_reshade_backward"""
+    """rgb of Engine.reshade with its gradient: forward = ra_reshade, backward = ra_reshade_backward.  light_xyz (L,3) or None: the light
+    positions the op is evaluated under.  The op carries them: a loss summed over several frames calls backward() once, so every frame's
+    ra_reshade_backward runs after the LAST frame's forward — the backward sets the positions of its own forward again."""
 
     @staticmethod
-    def forward(ctx, eng, ray_o, surf, norm, albedo, rough, lvis, ldot, probes):
-        rgb, _, _ = eng.reshade(ray_o, surf, norm, albedo, rough, lvis, ldot, probes, want_spec=False)
+    def forward(ctx, eng, ray_o, surf, norm, albedo, rough, lvis, ldot, probes, light_xyz):
         ctx.eng = eng
-        ctx.save_for_backward(ray_o, surf, norm, albedo, rough, lvis, ldot, probes)
+        ctx.moved = light_xyz is not None
+        if not ctx.moved:
+            rgb, _, _ = eng.reshade(ray_o, surf, norm, albedo, rough, lvis, ldot, probes, want_spec=False)
+            ctx.save_for_backward(ray_o, surf, norm, albedo, rough, lvis, ldot, probes)
+            return rgb
+        light_xyz = light_xyz.detach()
+        with eng.light_positions(light_xyz):
+            rgb, _, _ = eng.reshade(ray_o, surf, norm, albedo, rough, lvis, ldot, probes, want_spec=False)
+        ctx.save_for_backward(ray_o, surf, norm, albedo, rough, lvis, ldot, probes, light_xyz)
         return rgb
 
     @staticmethod
     def backward(ctx, d_rgb):
-        ray_o, surf, norm, albedo, rough, lvis, ldot, probes = ctx.saved_tensors
+        ray_o, surf, norm, albedo, rough, lvis, ldot, probes = ctx.saved_tensors[:8]
         want = tuple(ctx.needs_input_grad[i] for i in (4, 5, 8))
-        d_alb, d_rgh, d_prb = ctx.eng.reshade_backward(ray_o, surf, norm, albedo, rough, lvis, ldot, probes, d_rgb, want=want)
+        run = lambda: ctx.eng.reshade_backward(ray_o, surf, norm, albedo, rough, lvis, ldot, probes, d_rgb, want=want)
+        if ctx.moved:
+            with ctx.eng.light_positions(ctx.saved_tensors[8]):
+                d_alb, d_rgh, d_prb = run()
+        else:
+            d_alb, d_rgh, d_prb = run()
         shaped = lambda g, like: None if g is None else g.reshape(like.shape).to(like.dtype)
-        return (None, None, None, None, shaped(d_alb, albedo), shaped(d_rgh, rough), None, None, shaped(d_prb, probes))
+        return (None, None, None, None, shaped(d_alb, albedo), shaped(d_rgh, rough), None, None, shaped(d_prb, probes), None)
 
 
-def reshade(eng, ray_o, surf, norm, albedo, rough, lvis, ldot, probes):
+def reshade(eng, ray_o, surf, norm, albedo, rough, lvis, ldot, probes, light_xyz=None):
     """Differentiable novel-light re-shade (novel_light_sphere_tracing.render_human :21-66): probes (n,h,w,3) -> rgb (n,P,3).
     Gradients reach albedo, rough and probes only — the relighting stage's (relight_trainer.py:113-118): geometry is frozen and the
-    light visibility was computed without gradients.  Engine.reshade is the plain (no-autograd) call."""
-    return _Reshade.apply(eng, ray_o, surf, norm, albedo, rough, lvis, ldot, probes)
+    light visibility was computed without gradients.  Engine.reshade is the plain (no-autograd) call.
+    light_xyz (L,3): shade under these light positions (inputs.xyz of render_human: light_xyz_ plus the trainer's noise,
+    relight_network.py:79-84) — lvis / ldot are the caller's, traced under the same positions (Engine.light_visibility).  The forward sets
+    them and the backward sets them again, whatever ran in between; both leave the engine at the LOADED positions.  None: the engine's
+    current positions, and no call beyond ra_reshade / ra_reshade_backward is made."""
+    return _Reshade.apply(eng, ray_o, surf, norm, albedo, rough, lvis, ldot, probes, light_xyz)
 
 
 class _MaterialHeads(torch.autograd.Function):

@@ -6,10 +6,15 @@ device.  Appends one JSON line to profiles/heads_train.jsonl.  A record, not a g
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_heads.py --out /dev/null --reps 5 --kernels-only      # a run of its own
     python tools/bench_heads.py --share DIR [--out ...]      # the heads kernels' share of that trace's kernel time, appended as a line
     python tools/bench_heads.py --regularisers [--out profiles/relight_reg.jsonl]      # the regularised step (fit_heads(regularisers=True))
+    python tools/bench_heads.py --light-noise [--out profiles/light_noise.jsonl]       # ... under the trainer's light-position noise
 
 --regularisers times, on the same frame: the step without regularisers (the figure above, `kernels`), the step of the trainer's loss with
 ra_canonical_features / ra_gaussian_entropy, and that step with the two entropy terms evaluated by torch (the reference's formulas under
 autograd on the same device tensors); and ra_canonical_features against ra_bigpose_features on the frame's samples.
+
+--light-noise times the regularised step of fit_heads on the same frame for three settings — light_noise off, on with all counted pixels,
+on with pixels_per_step = 1024 — and, for scale, one Engine.light_visibility call on all counted pixels and one render of the frame.
+Under rocprofv3 (a run of its own, a few --reps, --out /dev/null) --share DIR then names the kernels the added time goes to (`top`).
 
 Both variants are warmed up (code objects, ctx scratch, clocks), then timed interleaved with HIP events around a whole step; the median
 and the spread are reported.  Everything but the heads is shared: the composite in torch, ra_reshade and ra_reshade_backward.
@@ -122,6 +127,45 @@ def regularised_leg(args, eng, cfg, cache, theta, probe, fitting):
     return r
 
 
+def light_noise_leg(args, eng, cfg, net, batch, maps, theta, probe, fitting, render):
+    dev = eng.device
+    weights = fitting.regulariser_weights(cfg, True)
+    target = maps.rgb_map.reshape(-1, 3) * 0.9
+    with torch.no_grad():
+        still = fitting._frame_cache(eng, cfg, batch, maps, target, None, True)
+        moving = fitting._frame_cache(eng, cfg, batch, maps, target, None, True, retrace=True)
+    n, S = still.w.shape[0], still.S
+    xyz0 = fitting.loaded_light_xyz(net, cfg, dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    normal = lambda std, rows: torch.normal(0.0, float(std), (rows, 3), generator=gen, device=dev)
+
+    def step(c, noisy, pixels):
+        theta.grad = None
+        xyz = xyz0 + normal(cfg.light_xyz_noise_std, xyz0.shape[0]) if noisy else None
+        rows = torch.randperm(n, generator=gen, device=dev)[:pixels] if pixels else None
+        v, shade = fitting.step_frame(eng, c, probe, rows, xyz)
+        fitting.regularised_loss(eng, [v], theta, probe, weights, [normal(cfg.xyz_noise_std, v.cpts.shape[0])], shades=[shade])[0].backward()
+    sub = min(1024, n)
+    t = timed([('off', lambda: step(still, False, None)), ('on_all_pixels', lambda: step(moving, True, None)),
+               (f'on_{sub}_pixels', lambda: step(moving, True, sub)), (f'off_{sub}_pixels', lambda: step(still, False, sub))], args.reps)
+    if not args.kernels_only:
+        t.update(timed([('light_visibility_all_pixels', lambda: eng.light_visibility(moving.surf_pts, moving.norm_pts, moving.acc, moving.bbox, probe=probe)),
+                        ('render_frame', render)], max(3, args.reps // 4)))
+    eng.set_frame(batch)
+    r = dict(tool='bench_heads', kind='light_noise_step', size=args.size, hit_pixels=int(n), samples=int(n * S), lights=int(xyz0.shape[0]), reps=args.reps,
+             device=torch.cuda.get_device_name(0), light_xyz_noise_std=float(cfg.light_xyz_noise_std), weights=weights)
+    for k, v in t.items():
+        r[k + '_ms'] = round(median(v), 4)
+        r[k + '_ms_min_max'] = [round(min(v), 4), round(max(v), 4)]
+    r['on_all_over_off'] = round(r['on_all_pixels_ms'] / r['off_ms'], 3)
+    r[f'on_{sub}_over_off'] = round(r[f'on_{sub}_pixels_ms'] / r['off_ms'], 3)
+    r['note'] = ('one regularised loss + backward of fit_heads without the Adam update, fresh device noise per step; off: the cached visibility; '
+                 'on_*: lights moved and the visibility of the step\'s pixels traced again (Engine.light_visibility); light_visibility_all_pixels: that '
+                 'call alone; render_frame: one render of the frame (all stages, every probe of the batch); host launch overhead included')
+    return r
+
+
 def share(trace_dir):
     files = glob.glob(os.path.join(trace_dir, '**', '*kernel_stats.csv'), recursive=True)
     if not files:      # a rocpd database (rocprofv3's default output format): summarised by tools/rocpd_stats.py
@@ -139,8 +183,14 @@ def share(trace_dir):
             if k in name:
                 heads += ns
                 rows[k] = rows.get(k, 0.0) + ns
+    per = {}
+    for row in csv.DictReader(open(files[0])):
+        name = (row.get('Name') or row.get('KernelName') or '').replace('(anonymous namespace)::', '')
+        name = (name[5:] if name.startswith('void ') else name).split('(')[0].split('<')[0] or name      # the kernel's name without return type, template and argument lists
+        per[name] = per.get(name, 0.0) + float(row.get('TotalDurationNs') or row.get('TotalDuration(ns)') or 0)
+    top = [dict(kernel=k[:60], ms=round(v / 1e6, 3), share=round(v / total, 4)) for k, v in sorted(per.items(), key=lambda kv: -kv[1])[:8]] if total else []
     return dict(tool='bench_heads', kind='kernel_share', trace=os.path.basename(files[0]), kernel_time_ms=round(total / 1e6, 3),
-                heads_share=round(heads / total, 4) if total else None, heads_ms={k: round(v / 1e6, 3) for k, v in rows.items()},
+                heads_share=round(heads / total, 4) if total else None, heads_ms={k: round(v / 1e6, 3) for k, v in rows.items()}, top=top,
                 note='totals over the traced run: the frame is rendered once, then 3 warm-up steps and --reps timed ones')
 
 
@@ -152,7 +202,10 @@ def main():
     ap.add_argument('--kernels-only', action='store_true', help='time the kernel variant alone (for a kernel trace)')
     ap.add_argument('--share', help='directory of a rocprofv3 --kernel-trace --stats run of this script')
     ap.add_argument('--regularisers', action='store_true', help='time the regularised step (default --out profiles/relight_reg.jsonl)')
+    ap.add_argument('--light-noise', action='store_true', help='time the regularised step under light-position noise (default --out profiles/light_noise.jsonl)')
     args = ap.parse_args()
+    if args.light_noise and args.out == os.path.join('profiles', 'heads_train.jsonl'):
+        args.out = os.path.join('profiles', 'light_noise.jsonl')
     if args.regularisers and args.out == os.path.join('profiles', 'heads_train.jsonl'):
         args.out = os.path.join('profiles', 'relight_reg.jsonl')
     if args.share:
@@ -169,15 +222,25 @@ def main():
         net.load_state_dict(synthetic.make_state_dict(0, relight=True, cfg=cfg))
         net = net.to(dev).eval()
         batch = synthetic.to_device(synthetic.make_batch(args.size, args.size, seed=0, posed=True, n_novel_lights=1), dev)
-        maps = make_renderer(cfg, net).render(batch)['probe00']
+        renderer = make_renderer(cfg, net)
+        maps = renderer.render(batch)['probe00']
         eng = net.engine()
         probe = batch.novel_lights['probe00'].probe
         probe = (probe[0] if probe.ndim == 4 else probe).to(dev).float()
         with torch.no_grad():
             cache = [fitting._frame_cache(eng, cfg, batch, maps, maps.rgb_map.reshape(-1, 3) * 0.9, None, True)]
         theta = eng.heads_params().requires_grad_(True)
-        if args.regularisers:
-            line = json.dumps(regularised_leg(args, eng, cfg, cache, theta, probe, fitting))
+        if args.regularisers or args.light_noise:
+            if args.light_noise:
+                again = synthetic.to_device(synthetic.make_batch(args.size, args.size, seed=0, posed=True, n_novel_lights=1), dev)
+                box = again.wbounds.clone()
+
+                def fresh():
+                    again.wbounds.copy_(box)          # the renderer grows the box in place
+                    renderer.render(again)
+                line = json.dumps(light_noise_leg(args, eng, cfg, net, batch, maps, theta, probe, fitting, fresh))
+            else:
+                line = json.dumps(regularised_leg(args, eng, cfg, cache, theta, probe, fitting))
             print(line, flush=True)
             if args.out and args.out != '/dev/null':
                 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
