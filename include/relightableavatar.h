@@ -568,6 +568,37 @@ typedef struct ra_image_params {
 int ra_map_to_image(ra_ctx* ctx, const ra_image_params* p, const float* a_dev, const float* b_dev, const float* acc_dev,
                     const long long* pix_dev, int P, float* image_dev, float* alpha_dev, void* stream);
 
+/* ---- evaluation: the metrics of the reference's evaluator (lib/evaluators/base_evaluator.py) for one image pair --------------------
+ * pred / gt: P x 3 fp32, either all H*W pixels of the image (pix NULL, P == H*W) or a ray list with pix[i] = the flat pixel index of
+ * ray i (mask_at_box.nonzero()); a pixel no ray covers has bg_brightness in both images (:79-85).  The assembled images are never
+ * built.  out (4 doubles on the device, 8-byte aligned; e.g. one row of an N x 4 table):
+ *   out[0]  mse: the mean of (pred - gt)^2 over the H*W*3 values of the assembled images (cfg.eval_whole_img, the reference's default);
+ *           with mse_over_rays over the P*3 ray values (eval_whole_img = False, :94; P == 0 gives NaN)
+ *   out[1]  psnr = -10 log10(mse) (:26-29); +inf for mse == 0
+ *   out[2]  ssim: skimage.metrics.structural_similarity(pred, gt, channel_axis=-1, data_range=data_range) at its defaults — 7 x 7
+ *           uniform window, K1 = 0.01, K2 = 0.03, sample covariance, the mean over the windows that do not touch the border and
+ *           over the 3 channels.  With crop_to_mask the images are first cropped to the bounding rectangle of the nonzero pixels of
+ *           mask (H*W bytes; cv2.boundingRect, :32-39); crop_to_mask changes out[2] and out[3] only.  An image or rectangle narrower
+ *           or lower than 7 (an empty mask too), where skimage raises: NaN
+ *   out[3]  the number of windows averaged per channel (0 with the NaN)
+ * Inputs are read as fp32, all arithmetic after them is double.  Asynchronous on stream, no read-back, no synchronisation; scratch is
+ * allocated on the first call of a size only.  No float atomics: one partial per workgroup, added in index order, grids that depend
+ * on H and W alone — two identical calls are bit-identical, a ray list gives the bits of its assembled image in any ray order, and
+ * crop_to_mask gives the ssim bits of a call on the cropped arrays.
+ * pix values are NOT validated: a value outside [0, H*W) drops that ray (its pixel keeps bg) without an error, and of two rays on one
+ * pixel either may win.  Any ctx will do (no weights are read).
+ * Errors: "null argument", "bad sizes" (H, W < 1, H*W >= 2^30, P < 0, P > H*W), "pixel indices" (P != H*W without pix), "mask"
+ * (crop_to_mask without mask), "alignment" (out). */
+typedef struct ra_metrics_params {
+    int H, W;
+    float bg_brightness;    /* cfg.bg_brightness */
+    float data_range;       /* 1 in the reference */
+    int mse_over_rays;
+    int crop_to_mask;
+} ra_metrics_params;
+int ra_image_metrics(ra_ctx* ctx, const ra_metrics_params* p, const float* pred_dev, const float* gt_dev, const long long* pix_dev, int P,
+                     const unsigned char* mask_dev, double* out_dev /* 4 */, void* stream);
+
 /* ---- test hooks: stage outputs for the parity tests (tests/test_gpu_*.py); not used by renderers ---- */
 /* resd + sdf MLPs on given big-pose points: resd n x 3, sdf n, feat n x 256 (any may be NULL) */
 /* the current frame's key lights (ra_config.key_light_share): n_lights flags and every light's largest share of a probe's power */

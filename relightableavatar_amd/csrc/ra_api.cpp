@@ -1431,6 +1431,27 @@ int ra_map_to_image(ra_ctx* c, const ra_image_params* p, const float* a, const f
     return 0;
 }
 
+int ra_image_metrics(ra_ctx* c, const ra_metrics_params* p, const float* pred, const float* gt, const long long* pix, int P,
+                     const unsigned char* mask, double* out, void* stream) {
+    RA_CHECK(c && p && out, "ra_image_metrics: null argument");
+    RA_CHECK(p->H >= 1 && p->W >= 1 && (long long)p->H * p->W < (1ll << 30) && P >= 0 && P <= (long long)p->H * p->W, "ra_image_metrics: bad sizes");
+    RA_CHECK(P == 0 || (pred && gt), "ra_image_metrics: null argument (pred, gt)");
+    RA_CHECK(pix || P == p->H * p->W, "ra_image_metrics: without pixel indices the maps must hold all H*W pixels");
+    RA_CHECK(!p->crop_to_mask || mask, "ra_image_metrics: crop_to_mask needs the mask");
+    RA_CHECK(((uintptr_t)out & 7) == 0, "ra_image_metrics: bad alignment of out (doubles)");
+    RA_HIP(hipSetDevice(c->device));
+    int err = 0;
+    char* scratch = c->buf<char>("metrics", metrics_scratch_bytes(p->H, p->W, pix != nullptr), &err);
+    RA_CHECK(!err, "ra_image_metrics: out of device memory");
+    MetricsIO io{};
+    io.pred = pred; io.gt = gt; io.pix = pix; io.P = P; io.mask = mask; io.H = p->H; io.W = p->W;
+    io.bg = p->bg_brightness; io.data_range = p->data_range; io.mse_over_rays = p->mse_over_rays; io.crop_to_mask = p->crop_to_mask;
+    io.out = out; io.scratch = scratch;
+    launch_image_metrics(io, (hipStream_t)stream);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
 static void inv3x3(const double* m, double* o) {
     const double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];
     const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);

@@ -206,6 +206,21 @@ int entropy_grid(int n);
 size_t entropy_scratch_doubles(int n);
 void launch_gaussian_entropy(const float* x, int n, const float* d_value, float* value, float* d_x, double* scratch, hipStream_t s);
 
+// MSE, PSNR, SSIM of one image pair (ra_metrics.hip); scratch: metrics_scratch_bytes(H, W, pix != nullptr) bytes
+struct MetricsIO {
+    const float *pred, *gt;                               // P x 3
+    const long long* pix;                                 // nullable: the maps hold all H*W pixels
+    int P;
+    const unsigned char* mask;                            // H*W, read with crop_to_mask
+    int H, W;
+    float bg, data_range;
+    int mse_over_rays, crop_to_mask;
+    double* out;                                          // 4: mse, psnr, ssim, windows
+    void* scratch;
+};
+size_t metrics_scratch_bytes(int H, int W, bool ray_list);
+void launch_image_metrics(const MetricsIO& io, hipStream_t s);
+
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot
 void launch_scatter_maps(const int* hit_idx, const int* hit_count, int P, int premultiply, const float* acc_full,

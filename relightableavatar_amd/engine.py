@@ -9,8 +9,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import (check, ra_config, ra_counters, ra_frame, ra_ground_out, ra_ground_params, ra_pose_in, ra_pose_out, ra_render_out,
-                   ra_sphere_params, ra_trace_params)
+from ._lib import (check, ra_config, ra_counters, ra_frame, ra_ground_out, ra_ground_params, ra_metrics_params, ra_pose_in, ra_pose_out,
+                   ra_render_out, ra_sphere_params, ra_trace_params)
 from .base_utils import dotdict
 
 
@@ -468,6 +468,34 @@ class Engine:
         d_x = torch.empty(n, 3, device=d) if want_grad else None
         check(self.lib.ra_gaussian_entropy(self.ctx, _ptr(x), n, _ptr(d_value), _ptr(value), _ptr(d_x), self.stream), 'ra_gaussian_entropy')
         return value, d_x
+
+    def image_metrics(self, pred, gt, H, W, pix=None, mask=None, bg=0.0, mse_over_rays=False, out=None, data_range=1.0):
+        """pred, gt (P,3): all H*W pixels, or a ray list with pix (P,) int64 = the flat pixel of every ray (pixels without a ray hold bg
+        in both images) -> float64 device tensor [mse, psnr, ssim, windows] of the reference's evaluator (base_evaluator.py:71-104;
+        include/relightableavatar.h: ra_image_metrics).  mask (H*W, nonzero = inside): the SSIM is taken on the mask's bounding rectangle
+        (eval_whole_img = False).  out: a contiguous float64 (4,) device tensor to fill, e.g. a row of an (N,4) table.  Nothing is read
+        back and nothing synchronises."""
+        d = self.device
+        pred, gt = _f32(pred.reshape(-1, 3), d), _f32(gt.reshape(-1, 3), d)
+        P = pred.shape[0]
+        if gt.shape[0] != P:
+            raise ValueError('image_metrics: pred and gt differ in size')
+        if pix is not None:
+            pix = pix.detach().to(device=d, dtype=torch.int64).reshape(-1).contiguous()
+            if pix.numel() != P:
+                raise ValueError('image_metrics: one pixel index per ray')
+        if mask is not None:
+            mask = mask.detach().to(device=d).reshape(-1).ne(0).to(torch.uint8).contiguous()
+            if mask.numel() != H * W:
+                raise ValueError('image_metrics: the mask must have H*W entries')
+        if out is None:
+            out = torch.empty(4, dtype=torch.float64, device=d)
+        elif not (out.is_contiguous() and out.dtype == torch.float64 and out.device == d and tuple(out.shape) == (4,)):
+            raise ValueError('image_metrics: out must be a contiguous float64 (4,) tensor on the engine\'s device')
+        p = ra_metrics_params(H=int(H), W=int(W), bg_brightness=float(bg), data_range=float(data_range), mse_over_rays=int(bool(mse_over_rays)),
+                              crop_to_mask=int(mask is not None))
+        check(self.lib.ra_image_metrics(self.ctx, C.byref(p), _ptr(pred), _ptr(gt), _ptr(pix), P, _ptr(mask), _ptr(out), self.stream), 'ra_image_metrics')
+        return out
 
     # ------------------------------------------------------------------ measurement
     def counters(self) -> dotdict:
