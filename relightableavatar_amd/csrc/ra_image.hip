@@ -44,7 +44,9 @@ __global__ void pick_kernel(const float* __restrict__ sorted, const int* __restr
     const int n = n_dev ? *n_dev : n_host;
     const int kk = k < 1 ? 1 : (k > n ? n : k);
     stats[0] = n > 0 ? sorted[kk - 1] : 0.f;
-    stats[1] = n > 0 ? sorted[n - kk] : 1.f;
+    // topk(k, largest=True)[0].min(): torch.min carries a NaN, and topk ranks NaNs first, so ONE NaN among the values makes the upper
+    // quantile NaN, not only k of them (the NaNs sort to the end: the last value tells)
+    stats[1] = n > 0 ? (sorted[n - 1] != sorted[n - 1] ? sorted[n - 1] : sorted[n - kk]) : 1.f;
 }
 
 __global__ void compose_kernel(ImageJob j) {
