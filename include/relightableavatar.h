@@ -599,6 +599,41 @@ typedef struct ra_metrics_params {
 int ra_image_metrics(ra_ctx* ctx, const ra_metrics_params* p, const float* pred_dev, const float* gt_dev, const long long* pix_dev, int P,
                      const unsigned char* mask_dev, double* out_dev /* 4 */, void* stream);
 
+/* ---- evaluation: LPIPS, the fourth metric of the reference's evaluator (lib/evaluators/base_evaluator.py:19-24, 50-69) ---------------
+ * lpips.LPIPS() at its defaults — net 'alex', version '0.1', linear layers on, spatial = False, eval mode — on images in [0, 1] as the
+ * evaluator passes them (no normalize=True: the network sees [0, 1], not [-1, 1]):
+ *   x = (x - shift) / scale per channel; AlexNet's five convolutions (11/4/2 3->64, maxpool 3/2, 5/1/2 64->192, maxpool 3/2,
+ *   3/1/1 192->384, 384->256, 256->256), a tap after every ReLU; per tap k, n = f / (sqrt(sum_c f^2) + 1e-10) for both images and
+ *   r_k = mean over positions of sum_c lin_k[c] (n0 - n1)^2; lpips = r_0 + r_1 + r_2 + r_3 + r_4.
+ * The pretrained weights are not part of this project: ra_lpips_load takes a user-supplied set (HOST pointers, fp32: conv_w[k] in
+ * torch's (Cout, Cin, k, k) order, conv_b[k] (Cout), lin[k] (Cout, the bias-free 1 x 1 convolution), shift / scale), packs the
+ * convolutions into the order the kernel reads and uploads them; a second call replaces the set behind the calls already queued.
+ * ra_lpips_load synchronises the stream; ra_lpips_loaded returns 1 once a set is loaded (0 for a NULL ctx). */
+typedef struct ra_lpips_weights {
+    const float* conv_w[5];     /* (64,3,11,11) (192,64,5,5) (384,192,3,3) (256,384,3,3) (256,256,3,3) */
+    const float* conv_b[5];
+    const float* lin[5];        /* 64, 192, 384, 256, 256 */
+    float shift[3], scale[3];   /* lpips: -0.030 -0.088 -0.188 / 0.458 0.448 0.450 */
+} ra_lpips_weights;
+int ra_lpips_load(ra_ctx* ctx, const ra_lpips_weights* w, void* stream);
+int ra_lpips_loaded(ra_ctx* ctx);
+/* pred / gt / pix / P / mask and p->H, W, bg_brightness, crop_to_mask as in ra_image_metrics (image assembly and the crop to
+ * cv2.boundingRect(mask) are the ones of its SSIM); p->mse_over_rays and p->data_range are ignored.  out (6 doubles on the device,
+ * 8-byte aligned): out[0] the value, out[1..5] the per-tap terms r_0..r_4.  An image or rectangle below 31 in either dimension (an empty
+ * mask too), where torch raises in the second pool: six NaNs.
+ * The convolutions run in fp32 (fp32-input MFMA: one k-ordered fmaf chain per output), everything after the fp32 features in double.
+ * Asynchronous on stream, no read-back, no synchronisation, no float atomics; the host never learns the rectangle: every grid depends
+ * on H and W alone, and scratch is allocated on the first call of a size only.  Two identical calls are bit-identical, (pred, gt) and
+ * (gt, pred) agree bit for bit, identical images give six exact zeros, a ray list gives the bits of its assembled image in any ray
+ * order, and crop_to_mask gives the bits of a call on the cropped arrays.
+ * Errors: those of ra_image_metrics, and "lpips weights not loaded" (a NULL ctx holds none). */
+int ra_lpips(ra_ctx* ctx, const ra_metrics_params* p, const float* pred_dev, const float* gt_dev, const long long* pix_dev, int P,
+             const unsigned char* mask_dev, double* out_dev /* 6 */, void* stream);
+/* stage hook for the parity tests: one image's (H*W x 3 fp32, H, W >= 31) post-ReLU activations of tap 0..4 in (C, h, w) order */
+int ra_lpips_features(ra_ctx* ctx, const float* img_dev, int H, int W, int tap, float* out_dev, void* stream);
+/* output pixels (of both images together) per workgroup tile of the convolutions: the tests take their edge sizes from it */
+int ra_lpips_tile_m(void);
+
 /* ---- test hooks: stage outputs for the parity tests (tests/test_gpu_*.py); not used by renderers ---- */
 /* resd + sdf MLPs on given big-pose points: resd n x 3, sdf n, feat n x 256 (any may be NULL) */
 /* the current frame's key lights (ra_config.key_light_share): n_lights flags and every light's largest share of a probe's power */

@@ -90,6 +90,10 @@ class ra_metrics_params(C.Structure):
                 ('crop_to_mask', C.c_int)]
 
 
+class ra_lpips_weights(C.Structure):
+    _fields_ = [('conv_w', C.c_void_p * 5), ('conv_b', C.c_void_p * 5), ('lin', C.c_void_p * 5), ('shift', C.c_float * 3), ('scale', C.c_float * 3)]
+
+
 class ra_counters(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ('n_coarse', 'n_fine_sdf', 'n_fine_full', 'n_shadow_rays', 'n_hit_pixels', 'n_shaded', 'n_fine_sdf_wide', 'n_fine_sdf_comp')]
 
@@ -153,6 +157,11 @@ SYMBOLS = {
     'ra_map_to_image': (C.c_int, [C.c_void_p, C.POINTER(ra_image_params)] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ra_image_metrics': (C.c_int, [C.c_void_p, C.POINTER(ra_metrics_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    'ra_lpips_load': (C.c_int, [C.c_void_p, C.POINTER(ra_lpips_weights), C.c_void_p]),
+    'ra_lpips_loaded': (C.c_int, [C.c_void_p]),
+    'ra_lpips': (C.c_int, [C.c_void_p, C.POINTER(ra_metrics_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ra_lpips_features': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_lpips_tile_m': (C.c_int, []),
     'ra_gen_rays': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_float), C.c_void_p] + [C.c_void_p] * 5 +
                     [C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     'ra_debug_mlp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -90,6 +90,7 @@ int ra_ctx_destroy(ra_ctx* c) {
                       &c->adj_start, &c->adj_list, &c->adj_dfaces};
     for (DevBuf* b : bufs) b->release();
     c->key_mask.release(); c->key_share.release();
+    c->lpips_arena.release();
     for (auto& kv : c->scratch) kv.second.release();
     for (auto& e : c->ev_pool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (int k = 0; k < PinRing::n; ++k) if (c->pin.ev[k]) hipEventDestroy(c->pin.ev[k]);
@@ -1448,6 +1449,72 @@ int ra_image_metrics(ra_ctx* c, const ra_metrics_params* p, const float* pred, c
     io.bg = p->bg_brightness; io.data_range = p->data_range; io.mse_over_rays = p->mse_over_rays; io.crop_to_mask = p->crop_to_mask;
     io.out = out; io.scratch = scratch;
     launch_image_metrics(io, (hipStream_t)stream);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_lpips_tile_m(void) { return LPIPS_BM; }
+
+int ra_lpips_loaded(ra_ctx* c) { return c && c->lpips_loaded ? 1 : 0; }
+
+int ra_lpips_load(ra_ctx* c, const ra_lpips_weights* w, void* stream) {
+    RA_CHECK(c && w, "ra_lpips_load: null argument");
+    for (int k = 0; k < LPIPS_TAPS; ++k) RA_CHECK(w->conv_w[k] && w->conv_b[k] && w->lin[k], "ra_lpips_load: null argument (a weight pointer)");
+    for (int ch = 0; ch < 3; ++ch) RA_CHECK(w->scale[ch] != 0.f, "ra_lpips_load: a zero scale");
+    const LpipsArena a = lpips_arena();
+    std::vector<float>& h = c->lpips_host;
+    h.assign(a.total, 0.f);
+    for (int k = 0; k < LPIPS_TAPS; ++k) {
+        lpips_pack_conv(LPIPS_LAYERS[k], w->conv_w[k], h.data() + a.conv[k]);
+        std::copy(w->conv_b[k], w->conv_b[k] + LPIPS_LAYERS[k].cout, h.data() + a.bias[k]);
+        std::copy(w->lin[k], w->lin[k] + LPIPS_LAYERS[k].cout, h.data() + a.lin[k]);
+    }
+    std::copy(w->shift, w->shift + 3, h.data() + a.shift);
+    std::copy(w->scale, w->scale + 3, h.data() + a.scale);
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    RA_CHECK(!c->lpips_arena.ensure(a.total * sizeof(float)), "ra_lpips_load: out of device memory");
+    RA_HIP(hipMemcpyAsync(c->lpips_arena.p, h.data(), a.total * sizeof(float), hipMemcpyHostToDevice, s));     // behind the calls that read the old set
+    RA_HIP(hipStreamSynchronize(s));      // the staging vector may be rebuilt by the next call
+    c->lpips_loaded = true;
+    return 0;
+}
+
+int ra_lpips(ra_ctx* c, const ra_metrics_params* p, const float* pred, const float* gt, const long long* pix, int P, const unsigned char* mask,
+             double* out, void* stream) {
+    RA_CHECK(p && out, "ra_lpips: null argument");
+    RA_CHECK(ra_lpips_loaded(c), "ra_lpips: lpips weights not loaded");      // a null ctx holds none
+    RA_CHECK(p->H >= 1 && p->W >= 1 && (long long)p->H * p->W < (1ll << 30) && P >= 0 && P <= (long long)p->H * p->W, "ra_lpips: bad sizes");
+    RA_CHECK(P == 0 || (pred && gt), "ra_lpips: null argument (pred, gt)");
+    RA_CHECK(pix || P == p->H * p->W, "ra_lpips: without pixel indices the maps must hold all H*W pixels");
+    RA_CHECK(!p->crop_to_mask || mask, "ra_lpips: crop_to_mask needs the mask");
+    RA_CHECK(((uintptr_t)out & 7) == 0, "ra_lpips: bad alignment of out (doubles)");
+    RA_HIP(hipSetDevice(c->device));
+    int err = 0;
+    char* scratch = c->buf<char>("lpips", lpips_scratch_bytes(p->H, p->W, pix != nullptr), &err);
+    RA_CHECK(!err, "ra_lpips: out of device memory");
+    LpipsIO io{};
+    io.pred = pred; io.gt = gt; io.pix = pix; io.P = P; io.mask = mask; io.H = p->H; io.W = p->W;
+    io.bg = p->bg_brightness; io.crop_to_mask = p->crop_to_mask; io.out = out; io.scratch = scratch;
+    io.arena = c->lpips_arena.as<float>(); io.off = lpips_arena();
+    launch_lpips(io, (hipStream_t)stream);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_lpips_features(ra_ctx* c, const float* img, int H, int W, int tap, float* out, void* stream) {
+    RA_CHECK(img && out, "ra_lpips_features: null argument");
+    RA_CHECK(ra_lpips_loaded(c), "ra_lpips_features: lpips weights not loaded");
+    RA_CHECK(H >= LPIPS_MIN_SIDE && W >= LPIPS_MIN_SIDE && (long long)H * W < (1ll << 30) && tap >= 0 && tap < LPIPS_TAPS,
+             "ra_lpips_features: bad sizes (an image below 31 x 31 has no features; tap 0..4)");
+    RA_HIP(hipSetDevice(c->device));
+    int err = 0;
+    char* scratch = c->buf<char>("lpips", lpips_scratch_bytes(H, W, false), &err);
+    RA_CHECK(!err, "ra_lpips_features: out of device memory");
+    LpipsIO io{};
+    io.pred = img; io.gt = img; io.P = H * W; io.H = H; io.W = W; io.scratch = scratch;
+    io.arena = c->lpips_arena.as<float>(); io.off = lpips_arena();
+    launch_lpips_features(io, tap, out, (hipStream_t)stream);
     RA_HIP(hipGetLastError());
     return 0;
 }

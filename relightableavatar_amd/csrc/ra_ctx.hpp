@@ -83,6 +83,10 @@ struct ra_ctx {
     DevBuf key_mask, key_share;   // (key_share: every light's largest share of a probe's power among the frame's probes)
     bool key_valid = false;       // the flags were computed for the probes this frame is shaded with
     bool key_external = false;    // ... by ra_set_key_probes (the novel-light renderer: every probe of the re-shade); else per render call
+    // LPIPS (ra_lpips_load): the packed AlexNet / lin weights; host copy = staging of the upload
+    DevBuf lpips_arena;
+    std::vector<float> lpips_host;
+    bool lpips_loaded = false;
     // frame
     FrameState fr{};
     DevBuf fR, fTh, fvertA, fpverts4, fpnorm, ftverts, fbias_r0, fbias_r4, fbias_c3, fcond, fbvh_pts, fbvh_pairs, fbvh_order;

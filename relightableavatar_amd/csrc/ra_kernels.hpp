@@ -1,6 +1,7 @@
 // Launchers of the non-MLP kernels (ra_hdq.hip, ra_trace.hip).
 #pragma once
 #include "ra_common.hpp"
+#include "ra_lpips_pack.hpp"
 
 // where the query points of a pass come from
 struct RaySet {
@@ -220,6 +221,26 @@ struct MetricsIO {
 };
 size_t metrics_scratch_bytes(int H, int W, bool ray_list);
 void launch_image_metrics(const MetricsIO& io, hipStream_t s);
+
+// LPIPS (AlexNet) of one image pair (ra_lpips.hip); scratch: lpips_scratch_bytes(H, W, pix != nullptr) bytes
+struct LpipsIO {
+    const float *pred, *gt;                               // P x 3
+    const long long* pix;                                 // nullable: the maps hold all H*W pixels
+    int P;
+    const unsigned char* mask;                            // H*W, read with crop_to_mask
+    int H, W;
+    float bg;
+    int crop_to_mask;
+    double* out;                                          // 6: the value, the five per-tap terms
+    void* scratch;
+    const float* arena;                                   // the packed weights on the device (ra_lpips_pack.hpp: lpips_arena())
+    LpipsArena off;
+};
+size_t lpips_scratch_bytes(int H, int W, bool ray_list);
+void launch_lpips(const LpipsIO& io, hipStream_t s);
+// one image (io.pred == io.gt: H*W x 3, no ray list, no crop; H, W >= LPIPS_MIN_SIDE): the post-ReLU activations of one tap in (C, h, w) order
+void launch_lpips_features(const LpipsIO& io, int tap, float* out, hipStream_t s);
+void lpips_feature_shape(int H, int W, int tap, int* C, int* h, int* w);
 
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot

@@ -28,6 +28,7 @@
 // No float atomics.  Tiles beyond the rectangle write an exact 0, so cropping to a mask and handing in the cropped arrays add the same
 // numbers in the same order; the pixel sums run in pixel order, so the order of the rays does not matter.
 #include "ra_kernels.hpp"
+#include "ra_fetch.hpp"      // Images, fetch, pair_prep_kernel, pair_scatter_kernel
 #include <algorithm>
 #include <climits>
 
@@ -39,24 +40,6 @@ constexpr int MT_WIN = 7;
 constexpr int MT_LD = MT_TILE + MT_WIN - 1;   // pixels per tile side: 38
 constexpr int MT_NP = MT_WIN * MT_WIN;
 constexpr int MT_PIX = 2048;                  // pixels per workgroup of the pixel pass
-
-struct Images {
-    const float *pred, *gt;
-    const int* inv;       // pixel -> ray (-1: no ray), or nullptr: the maps are full images
-    float bg;
-    int W;
-};
-
-// the one reader of both layouts: channel values of pixel (r, c) of the two assembled images
-__device__ __forceinline__ void fetch(const Images& im, int r, int c, float (&x)[3], float (&y)[3]) {
-    long long k = (long long)r * im.W + c;
-    if (im.inv) k = im.inv[k];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        x[ch] = k < 0 ? im.bg : im.pred[3 * k + ch];
-        y[ch] = k < 0 ? im.bg : im.gt[3 * k + ch];
-    }
-}
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -71,23 +54,6 @@ __device__ __forceinline__ double block_sum(double v, double* lds) {
     if ((tid & 63) == 0) lds[tid >> 6] = w;
     __syncthreads();
     return ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
-
-__global__ __launch_bounds__(MT_T) void metrics_prep_kernel(int* __restrict__ inv, int n_inv, int* __restrict__ rect, int H, int W, int crop) {
-    for (int i = blockIdx.x * MT_T + threadIdx.x; i < n_inv; i += gridDim.x * MT_T) inv[i] = -1;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        rect[0] = crop ? INT_MAX : 0;
-        rect[1] = crop ? INT_MAX : 0;
-        rect[2] = crop ? -1 : W - 1;
-        rect[3] = crop ? -1 : H - 1;
-    }
-}
-
-__global__ __launch_bounds__(MT_T) void metrics_scatter_kernel(const long long* __restrict__ pix, int P, int HW, int* __restrict__ inv) {
-    for (int i = blockIdx.x * MT_T + threadIdx.x; i < P; i += gridDim.x * MT_T) {
-        const long long p = pix[i];
-        if ((unsigned long long)p < (unsigned long long)HW) inv[p] = i;      // a pixel outside the image: the ray is dropped
-    }
 }
 
 __global__ __launch_bounds__(MT_T) void metrics_pixel_kernel(Images im, int HW, const unsigned char* __restrict__ mask, int* __restrict__ rect,
@@ -235,10 +201,10 @@ void launch_image_metrics(const MetricsIO& io, hipStream_t s) {
     double* rows = pssim + (size_t)ntx * nty;
     int* inv = ray_list ? (int*)(base + 32 + align_up(sizeof(double) * ((size_t)n_mse + (size_t)ntx * nty + nty))) : nullptr;
     const Images im{io.pred, io.gt, inv, io.bg, io.W};
-    const int fill_grid = ray_list ? std::min(1024, (HW + MT_T - 1) / MT_T) : 1;
-    hipLaunchKernelGGL(metrics_prep_kernel, dim3(fill_grid), dim3(MT_T), 0, s, inv, ray_list ? HW : 0, rect, io.H, io.W, io.crop_to_mask);
+    const int fill_grid = ray_list ? std::min(1024, (HW + FETCH_T - 1) / FETCH_T) : 1;
+    hipLaunchKernelGGL(pair_prep_kernel, dim3(fill_grid), dim3(FETCH_T), 0, s, inv, ray_list ? HW : 0, rect, io.H, io.W, io.crop_to_mask);
     if (ray_list && io.P > 0)
-        hipLaunchKernelGGL(metrics_scatter_kernel, dim3(std::min(1024, (io.P + MT_T - 1) / MT_T)), dim3(MT_T), 0, s, io.pix, io.P, HW, inv);
+        hipLaunchKernelGGL(pair_scatter_kernel, dim3(std::min(1024, (io.P + FETCH_T - 1) / FETCH_T)), dim3(FETCH_T), 0, s, io.pix, io.P, HW, inv);
     hipLaunchKernelGGL(metrics_pixel_kernel, dim3(n_mse), dim3(MT_T), 0, s, im, HW, io.crop_to_mask ? io.mask : nullptr, rect, pmse);
     const double c1 = (0.01 * (double)io.data_range) * (0.01 * (double)io.data_range), c2 = (0.03 * (double)io.data_range) * (0.03 * (double)io.data_range);
     hipLaunchKernelGGL(metrics_ssim_kernel, dim3(ntx, nty), dim3(MT_T), 0, s, im, (const int*)rect, c1, c2, pssim);

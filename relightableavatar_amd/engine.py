@@ -9,8 +9,9 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import (check, ra_config, ra_counters, ra_frame, ra_ground_out, ra_ground_params, ra_metrics_params, ra_pose_in, ra_pose_out,
+from ._lib import (check, ra_config, ra_counters, ra_frame, ra_ground_out, ra_ground_params, ra_lpips_weights, ra_metrics_params, ra_pose_in, ra_pose_out,
                    ra_render_out, ra_sphere_params, ra_trace_params)
+from . import lpips_weights
 from .base_utils import dotdict
 
 
@@ -495,6 +496,67 @@ class Engine:
         p = ra_metrics_params(H=int(H), W=int(W), bg_brightness=float(bg), data_range=float(data_range), mse_over_rays=int(bool(mse_over_rays)),
                               crop_to_mask=int(mask is not None))
         check(self.lib.ra_image_metrics(self.ctx, C.byref(p), _ptr(pred), _ptr(gt), _ptr(pix), P, _ptr(mask), _ptr(out), self.stream), 'ra_image_metrics')
+        return out
+
+    def lpips_load(self, state_dict):
+        """load an LPIPS (AlexNet) weight set: `lpips.LPIPS().state_dict()`, torchvision's alexnet keys plus the lin* keys, or the neutral
+        conv{k}.weight / conv{k}.bias / lin{k}.weight layout (lpips_weights.py holds the table; a missing key or a wrong shape raises and
+        lists the expected names and shapes).  A second call replaces the set."""
+        w = lpips_weights.resolve(state_dict)
+        c = ra_lpips_weights()
+        for k in range(lpips_weights.TAPS):
+            c.conv_w[k] = w[f'conv{k}.weight'].ctypes.data
+            c.conv_b[k] = w[f'conv{k}.bias'].ctypes.data
+            c.lin[k] = w[f'lin{k}.weight'].ctypes.data
+        for ch in range(3):
+            c.shift[ch], c.scale[ch] = float(w['shift'][ch]), float(w['scale'][ch])
+        check(self.lib.ra_lpips_load(self.ctx, C.byref(c), self.stream), 'ra_lpips_load')
+
+    def lpips_loaded(self):
+        return bool(self.lib.ra_lpips_loaded(self.ctx))
+
+    def lpips(self, pred, gt, H, W, pix=None, mask=None, bg=0.0, out=None):
+        """pred, gt, pix, mask, bg as in image_metrics -> float64 device tensor [lpips, r_0 .. r_4]: lpips.LPIPS() (AlexNet, 0.1) on the
+        two assembled images in [0, 1] as the reference's evaluator calls it (base_evaluator.py:50-69), and its five per-tap terms.
+        mask: the images are first cropped to its bounding rectangle.  Below 31 in a dimension: six NaNs.  out: a contiguous float64
+        (6,) device tensor to fill.  Nothing is read back and nothing synchronises.  Needs lpips_load()."""
+        d = self.device
+        pred, gt = _f32(pred.reshape(-1, 3), d), _f32(gt.reshape(-1, 3), d)
+        P = pred.shape[0]
+        if gt.shape[0] != P:
+            raise ValueError('lpips: pred and gt differ in size')
+        if pix is not None:
+            pix = pix.detach().to(device=d, dtype=torch.int64).reshape(-1).contiguous()
+            if pix.numel() != P:
+                raise ValueError('lpips: one pixel index per ray')
+        if mask is not None:
+            mask = mask.detach().to(device=d).reshape(-1).ne(0).to(torch.uint8).contiguous()
+            if mask.numel() != H * W:
+                raise ValueError('lpips: the mask must have H*W entries')
+        if out is None:
+            out = torch.empty(6, dtype=torch.float64, device=d)
+        elif not (out.is_contiguous() and out.dtype == torch.float64 and out.device == d and tuple(out.shape) == (6,)):
+            raise ValueError('lpips: out must be a contiguous float64 (6,) tensor on the engine\'s device')
+        p = ra_metrics_params(H=int(H), W=int(W), bg_brightness=float(bg), data_range=1.0, mse_over_rays=0, crop_to_mask=int(mask is not None))
+        check(self.lib.ra_lpips(self.ctx, C.byref(p), _ptr(pred), _ptr(gt), _ptr(pix), P, _ptr(mask), _ptr(out), self.stream), 'ra_lpips')
+        return out
+
+    def lpips_features(self, img, tap):
+        """img (H,W,3) in [0, 1] -> the post-ReLU activations of tap 0..4 as a (C,h,w) fp32 device tensor (stage hook of the parity tests)"""
+        d = self.device
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError('lpips_features: img must be (H, W, 3)')
+        H, W = int(img.shape[0]), int(img.shape[1])
+        if min(H, W) < 31 or not 0 <= int(tap) < lpips_weights.TAPS:
+            raise ValueError('lpips_features: an image below 31 x 31 has no features; tap 0..4')
+        img = _f32(img, d)
+        side = lambda n: (n - 7) // 4 + 1
+        pool = lambda n: (n - 3) // 2 + 1
+        h, w = side(H), side(W)
+        for _ in range(min(int(tap), 2)):
+            h, w = pool(h), pool(w)
+        out = torch.empty(lpips_weights.CONV_SHAPES[int(tap)][0], h, w, device=d)
+        check(self.lib.ra_lpips_features(self.ctx, _ptr(img), H, W, int(tap), _ptr(out), self.stream), 'ra_lpips_features')
         return out
 
     # ------------------------------------------------------------------ measurement

@@ -1,14 +1,20 @@
-"""Device-side mirror of the reference's evaluator: MSE, PSNR and SSIM of a rendered frame against the ground truth.
+"""Device-side mirror of the reference's evaluator: MSE, PSNR, SSIM and LPIPS of a rendered frame against the ground truth.
 
     Evaluator.evaluate(output, batch), Evaluator.summarize()      lib/evaluators/base_evaluator.py:71-129
     cfg.eval_whole_img                                            lib/config/config.py:215
 
 evaluate() queues one ra_image_metrics call per frame (Engine.image_metrics) into a growing device table and reads nothing back;
-summarize() does the only device-to-host copy, returns the means, keeps the per-frame lists in self.metrics (what the reference
+summarize() does the only device-to-host copies, returns the means, keeps the per-frame lists in self.metrics (what the reference
 saves as metrics.npy) and resets the evaluator.  There is no CPU fallback.
 
+When the engine holds an LPIPS weight set (Engine.lpips_load), evaluate() also queues one ra_lpips call per frame (Engine.lpips) into a
+second growing table, and summarize() returns a fourth key 'lpips'.  Without a loaded set nothing changes: three keys, no extra call.
+
 Scope, stated rather than implied:
-  - LPIPS is NOT mirrored: its pretrained network is not part of this project.  summarize() has no 'lpips' key — not a silent zero.
+  - LPIPS (:19-24, 50-69, 103-104) is lpips.LPIPS() at its defaults on the [0, 1] images, as the reference calls it (no normalize=True),
+    assembled and cropped like the SSIM's.  Its pretrained weights are NOT part of this project: the user loads a state dict
+    (INTEGRATION.md).  Without one summarize() has no 'lpips' key — not a silent zero.  Frames evaluated before the weights were loaded
+    and frames after them must not be mixed in one summary: summarize() refuses unequal counts.
   - Writing images (self.visualize, the metrics.npy file) stays out, as in the visualiser.
   - A batch with crop_bbox is refused: the reference's own two-argument fill_image call (:41-43) raises a TypeError there, so there is
     nothing to mirror.
@@ -32,6 +38,8 @@ class Evaluator:
         self.metrics = None      # the per-frame lists of the last summary
         self._table = None
         self._n = 0
+        self._lpips = None       # the second table: (N, 6) [lpips, r_0 .. r_4] per frame, filled while the engine holds LPIPS weights
+        self._n_lpips = 0
 
     def __len__(self):
         return self._n
@@ -44,6 +52,15 @@ class Evaluator:
             self._table = grown
         self._n += 1
         return self._table[self._n - 1]
+
+    def _lpips_row(self, dev):
+        if self._lpips is None or self._n_lpips == self._lpips.shape[0]:
+            grown = torch.empty(self._n_lpips + self.GROW, 6, dtype=torch.float64, device=dev)
+            if self._n_lpips:
+                grown[:self._n_lpips].copy_(self._lpips)
+            self._lpips = grown
+        self._n_lpips += 1
+        return self._lpips[self._n_lpips - 1]
 
     def evaluate(self, output, batch, engine=None):
         cfg = config.active_cfg()
@@ -81,11 +98,17 @@ class Evaluator:
             pix = pix[:P]
         eng.image_metrics(pred, gt, H, W, pix=pix, mask=None if whole else mask, bg=float(cfg.bg_brightness), mse_over_rays=not whole,
                           out=self._row(dev))
+        if eng.lpips_loaded():
+            eng.lpips(pred, gt, H, W, pix=pix, mask=None if whole else mask, bg=float(cfg.bg_brightness), out=self._lpips_row(dev))
 
     def summarize(self):
         if self._n == 0:
             raise RuntimeError('Evaluator.summarize: no frame was evaluated')
+        if self._n_lpips not in (0, self._n):
+            raise RuntimeError(f'Evaluator.summarize: {self._n} frames but {self._n_lpips} with LPIPS: the weights were loaded between frames')
         rows = self._table[:self._n].cpu().numpy()            # the one device-to-host copy
         self.metrics = {'mse': rows[:, 0].tolist(), 'psnr': rows[:, 1].tolist(), 'ssim': rows[:, 2].tolist()}      # the reference's metrics.npy
-        self._table, self._n = None, 0
+        if self._n_lpips:
+            self.metrics['lpips'] = self._lpips[:self._n_lpips, 0].cpu().numpy().tolist()      # ... and one more with LPIPS weights loaded
+        self._table, self._n, self._lpips, self._n_lpips = None, 0, None, 0
         return {k: float(np.mean(v)) for k, v in self.metrics.items()}
