@@ -21,9 +21,13 @@ struct HostNets {
     std::vector<float> light_xyz, light_area, light_sharp;
 };
 
-struct DevBuf {
+struct DevBuf {             // owns its device block: freed with the buffer (on the device that is current then); movable, not copyable
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+    ~DevBuf() { release(); }
     int ensure(size_t need);   // grow-only; returns non-zero on failure
     void release();
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
@@ -34,6 +38,7 @@ struct ra_gate {
     int device = 0;
     hipEvent_t done = nullptr;      // end of the last stage submitted through the gate
     bool armed = false;
+    ~ra_gate() { if (done) hipEventDestroy(done); }
 };
 
 // Pinned host staging for small per-frame inputs (bone poses): a slot is filled by the host, copied H2D asynchronously and may be refilled
@@ -60,6 +65,9 @@ struct HintSlot {
     int n_valid = 0;
     std::vector<int> vals;
 };
+
+// what a timed launch was (Timer, ra_get_kernel_time)
+enum TimerKind { T_K3_WIDE = 0, T_K4 = 1, T_K3_NARROW = 2, T_K3C = 3 };      // 8-wave K3, full query (K4 pair), narrow K3, K3C
 
 struct ra_ctx {
     int device = 0;
@@ -89,7 +97,7 @@ struct ra_ctx {
     bool lpips_loaded = false;
     // frame
     FrameState fr{};
-    DevBuf fR, fTh, fvertA, fpverts4, fpnorm, ftverts, fbias_r0, fbias_r4, fbias_c3, fcond, fbvh_pts, fbvh_pairs, fbvh_order;
+    DevBuf fvertA, fpverts4, fbias_r0, fbias_r4, fbias_c3, fbvh_pts, fbvh_pairs, fbvh_order;
     bool use_bvh = true;
     // N3: vertex -> incident corners of the template mesh (built once per faces array)
     DevBuf adj_start, adj_list, adj_dfaces;
@@ -97,17 +105,19 @@ struct ra_ctx {
     int adj_n_faces = 0, adj_n_verts = 0;
     // scratch (grow-only)
     std::map<std::string, DevBuf> scratch;
-    DevBuf dcounters;       // DevCounters (64 B) + at byte 128: the int counters of a chunk (ra_api.cpp: CNT_*, fine-count slots)
+    DevBuf dcounters;       // DevCounters (64 B) + at byte 128: the int counters of a chunk (ra_api_impl.hpp: CNT_*; ra_api.cpp: the fine-count slots)
     int fc_next = 0;        // next unused fine-count slot (each hdq pass takes a fresh, still-zero one)
     bool fc_wrapped = false;
     bool cnt_zero = false;  // the named counters (hit / ray / sample counts) were zeroed by the chunk's bulk memset
     // host-side counters
-    uint64_t n_coarse = 0, n_shaded = 0;
+    uint64_t n_shaded = 0;
     // timing of the fused MLP launches
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    std::vector<int> ev_kind;      // 0: 8-wave K3 launch, 2: narrow K3, 3: K3C, 1: full query (K4 pair)
+    std::vector<TimerKind> ev_kind;
     size_t ev_used = 0;
+
+    ~ra_ctx();      // the events and pinned blocks of ev_pool, pin and hints; the DevBufs free themselves (ra_ctx_destroy makes the device current)
 
     template <typename T> T* buf(const std::string& name, size_t count, int* err) {
         DevBuf& b = scratch[name];

@@ -259,6 +259,7 @@ void launch_volume_composite(const float* raw, int C, const float* near_, const 
                              const ra_render_out& out, const int* perm, hipStream_t s);
 void launch_fill(float* p, size_t n, float v, hipStream_t s);
 void launch_iota(int* idx, int n, int* count, hipStream_t s);      // idx[i] = i, *count = n
+void launch_gather_rows(const int* hit_idx, const int* hit_count, int P, const float* src, int C, float* dst, hipStream_t s);   // row k of dst = row hit_idx[k] of src, k < *hit_count
 // per point: w2b = big_A_bw @ affine_inverse(A_bw) @ affine_inverse([R|Th]) (or its affine_inverse) from the blended rows of the coarse level
 void launch_bigpose_compose(const float* mats, const float* d2, int n, float blend_radius, const float* R, const float* Th, int invert, float* out,
                             hipStream_t s);

@@ -23,6 +23,27 @@ def _f32(t: torch.Tensor, device) -> torch.Tensor:
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+def _bbox6(bbox6):
+    return (C.c_float * 6)(*[float(v) for v in bbox6])
+
+
+def _probe_hw(probe):
+    """(h, w) of an (h,w,3) probe; (0, 0) without one"""
+    return (probe.shape[0], probe.shape[1]) if probe is not None else (0, 0)
+
+
+def _set_box_tables(params, boxes, box_start):
+    """the n_boxes / boxes / box_start tables of ra_sphere_params / ra_ground_params (one box: none); returns the arrays params points
+    into, which the caller holds until the library call has returned"""
+    if boxes is not None and len(boxes) > 1:
+        flat = (C.c_float * (6 * len(boxes)))(*[float(v) for b in boxes for v in b])
+        starts = (C.c_int * (len(boxes) + 1))(*[int(v) for v in box_start])
+        params.n_boxes, params.boxes, params.box_start = len(boxes), C.cast(flat, C.POINTER(C.c_float)), C.cast(starts, C.POINTER(C.c_int))
+        return flat, starts
+    params.n_boxes, params.boxes, params.box_start = 0, None, None
+    return None
+
+
 class RaysPending:
     """rays generated on the device whose count has not been read yet (Engine.gen_rays_async)"""
 
@@ -205,14 +226,9 @@ class Engine:
         boxes / box_start: several of the reference's chunks in this one call, the shadow rays of ray r clipped against the box of its own chunk."""
         P = ray_o.shape[0]
         ro = ra_render_out(**{k: _ptr(outs.get(k)) for k in _lib.RENDER_OUT_KEYS})
-        bb = (C.c_float * 6)(*[float(v) for v in bbox6]) if bbox6 is not None else None
-        ph, pw = (probe.shape[0], probe.shape[1]) if probe is not None else (0, 0)
-        if boxes is not None and len(boxes) > 1:
-            flat = (C.c_float * (6 * len(boxes)))(*[float(v) for b in boxes for v in b])
-            starts = (C.c_int * (len(boxes) + 1))(*[int(v) for v in box_start])
-            params.n_boxes, params.boxes, params.box_start = len(boxes), C.cast(flat, C.POINTER(C.c_float)), C.cast(starts, C.POINTER(C.c_int))
-        else:
-            params.n_boxes, params.boxes, params.box_start = 0, None, None
+        bb = _bbox6(bbox6) if bbox6 is not None else None
+        ph, pw = _probe_hw(probe)
+        tables = _set_box_tables(params, boxes, box_start)      # alive across the call below
         check(self.lib.ra_render_sphere_chunk(self.ctx, _ptr(ray_o), _ptr(ray_d), _ptr(near), _ptr(far), P, bb, _ptr(probe), ph, pw,
                                               C.byref(params), C.byref(ro), self.stream), 'ra_render_sphere_chunk')
 
@@ -231,13 +247,8 @@ class Engine:
         boxes / box_start: several of the reference's chunks in this one call, pixel r clipped against the box of its own chunk."""
         P = ray_o.shape[0]
         go = ra_ground_out(**{k: _ptr(outs.get(k)) for k in _lib.GROUND_OUT_KEYS})
-        bb = (C.c_float * 6)(*[float(v) for v in bbox6])
-        if boxes is not None and len(boxes) > 1:
-            flat = (C.c_float * (6 * len(boxes)))(*[float(v) for b in boxes for v in b])
-            starts = (C.c_int * (len(boxes) + 1))(*[int(v) for v in box_start])
-            params.n_boxes, params.boxes, params.box_start = len(boxes), C.cast(flat, C.POINTER(C.c_float)), C.cast(starts, C.POINTER(C.c_int))
-        else:
-            params.n_boxes, params.boxes, params.box_start = 0, None, None
+        bb = _bbox6(bbox6)
+        tables = _set_box_tables(params, boxes, box_start)      # alive across the call below
         check(self.lib.ra_render_ground_chunk(self.ctx, _ptr(ray_o), _ptr(ray_d), _ptr(acc), P, bb, _ptr(probe), probe.shape[0],
                                               probe.shape[1], C.byref(params), C.byref(go), self.stream), 'ra_render_ground_chunk')
 
@@ -304,8 +315,8 @@ class Engine:
         if m == 0:      # nothing to trace (an empty tensor has no address to hand over)
             return lvis, ldot
         probe = None if probe is None else _f32(probe[0] if probe.ndim == 4 else probe, dv)
-        ph, pw = (probe.shape[0], probe.shape[1]) if probe is not None else (0, 0)
-        bb = (C.c_float * 6)(*[float(v) for v in bbox6])
+        ph, pw = _probe_hw(probe)
+        bb = _bbox6(bbox6)
         p = self.sphere_params() if params is None else params
         check(self.lib.ra_light_visibility(self.ctx, _ptr(surf), _ptr(norm), _ptr(acc), n, _ptr(rows), m if rows is not None else 0, bb, _ptr(probe),
                                            ph, pw, C.byref(p), _ptr(lvis), _ptr(ldot), self.stream), 'ra_light_visibility')
@@ -348,13 +359,18 @@ class Engine:
         check(self.lib.ra_render_volume_chunk(self.ctx, _ptr(ray_o), _ptr(ray_d), _ptr(near), _ptr(far), P, n_samples, dist_th,
                                               C.byref(ro), self.stream), 'ra_render_volume_chunk')
 
-    def reshade(self, ray_o, surf, norm, albedo, rough, lvis, ldot, probes, want_spec=True):
-        """probes (n,h,w,3) -> rgb, shade, spec each (n,P,3)."""
+    def _reshade_inputs(self, ray_o, surf, norm, albedo, rough, lvis, ldot, probes):
+        """the inputs of reshade / reshade_backward as contiguous fp32 device tensors: [ray_o, surf, norm, albedo, rough], lvis, ldot, probes"""
         d = self.device
         a = [_f32(t, d) for t in (ray_o.reshape(-1, 3), surf.reshape(-1, 3), norm.reshape(-1, 3), albedo.reshape(-1, 3), rough.reshape(-1))]
         P = a[0].shape[0]
-        lvis, ldot = _f32(lvis.reshape(P, -1), d), _f32(ldot.reshape(P, -1), d)
-        probes = _f32(probes, d)
+        return a, _f32(lvis.reshape(P, -1), d), _f32(ldot.reshape(P, -1), d), _f32(probes, d)
+
+    def reshade(self, ray_o, surf, norm, albedo, rough, lvis, ldot, probes, want_spec=True):
+        """probes (n,h,w,3) -> rgb, shade, spec each (n,P,3)."""
+        d = self.device
+        a, lvis, ldot, probes = self._reshade_inputs(ray_o, surf, norm, albedo, rough, lvis, ldot, probes)
+        P = a[0].shape[0]
         n, ph, pw = probes.shape[0], probes.shape[1], probes.shape[2]
         rgb, shade = torch.empty(n, P, 3, device=d), torch.empty(n, P, 3, device=d)
         spec = torch.empty(n, P, 3, device=d) if want_spec else None
@@ -366,10 +382,8 @@ class Engine:
         """backward of reshade's rgb: d_rgb (n,P,3) -> d_albedo (P,3), d_rough (P,), d_probes (n,h,w,3); want: which of the three
         to compute (the others are None)."""
         d = self.device
-        a = [_f32(t, d) for t in (ray_o.reshape(-1, 3), surf.reshape(-1, 3), norm.reshape(-1, 3), albedo.reshape(-1, 3), rough.reshape(-1))]
+        a, lvis, ldot, probes = self._reshade_inputs(ray_o, surf, norm, albedo, rough, lvis, ldot, probes)
         P = a[0].shape[0]
-        lvis, ldot = _f32(lvis.reshape(P, -1), d), _f32(ldot.reshape(P, -1), d)
-        probes = _f32(probes, d)
         n, ph, pw = probes.shape[0], probes.shape[1], probes.shape[2]
         d_rgb = _f32(d_rgb.reshape(n, P, 3), d)
         # zeros, not empty: a call with P == 0 or n == 0 writes nothing, and the gradient of an empty sum is 0
@@ -470,29 +484,35 @@ class Engine:
         check(self.lib.ra_gaussian_entropy(self.ctx, _ptr(x), n, _ptr(d_value), _ptr(value), _ptr(d_x), self.stream), 'ra_gaussian_entropy')
         return value, d_x
 
+    def _image_pair(self, who, pred, gt, H, W, pix, mask, out, n_out):
+        """the image pair of image_metrics / lpips on the device, checked: pred, gt, pix, mask, out (allocated with n_out doubles if None)"""
+        d = self.device
+        pred, gt = _f32(pred.reshape(-1, 3), d), _f32(gt.reshape(-1, 3), d)
+        P = pred.shape[0]
+        if gt.shape[0] != P:
+            raise ValueError(f'{who}: pred and gt differ in size')
+        if pix is not None:
+            pix = pix.detach().to(device=d, dtype=torch.int64).reshape(-1).contiguous()
+            if pix.numel() != P:
+                raise ValueError(f'{who}: one pixel index per ray')
+        if mask is not None:
+            mask = mask.detach().to(device=d).reshape(-1).ne(0).to(torch.uint8).contiguous()
+            if mask.numel() != H * W:
+                raise ValueError(f'{who}: the mask must have H*W entries')
+        if out is None:
+            out = torch.empty(n_out, dtype=torch.float64, device=d)
+        elif not (out.is_contiguous() and out.dtype == torch.float64 and out.device == d and tuple(out.shape) == (n_out,)):
+            raise ValueError(f'{who}: out must be a contiguous float64 ({n_out},) tensor on the engine\'s device')
+        return pred, gt, pix, mask, out
+
     def image_metrics(self, pred, gt, H, W, pix=None, mask=None, bg=0.0, mse_over_rays=False, out=None, data_range=1.0):
         """pred, gt (P,3): all H*W pixels, or a ray list with pix (P,) int64 = the flat pixel of every ray (pixels without a ray hold bg
         in both images) -> float64 device tensor [mse, psnr, ssim, windows] of the reference's evaluator (base_evaluator.py:71-104;
         include/relightableavatar.h: ra_image_metrics).  mask (H*W, nonzero = inside): the SSIM is taken on the mask's bounding rectangle
         (eval_whole_img = False).  out: a contiguous float64 (4,) device tensor to fill, e.g. a row of an (N,4) table.  Nothing is read
         back and nothing synchronises."""
-        d = self.device
-        pred, gt = _f32(pred.reshape(-1, 3), d), _f32(gt.reshape(-1, 3), d)
+        pred, gt, pix, mask, out = self._image_pair('image_metrics', pred, gt, H, W, pix, mask, out, 4)
         P = pred.shape[0]
-        if gt.shape[0] != P:
-            raise ValueError('image_metrics: pred and gt differ in size')
-        if pix is not None:
-            pix = pix.detach().to(device=d, dtype=torch.int64).reshape(-1).contiguous()
-            if pix.numel() != P:
-                raise ValueError('image_metrics: one pixel index per ray')
-        if mask is not None:
-            mask = mask.detach().to(device=d).reshape(-1).ne(0).to(torch.uint8).contiguous()
-            if mask.numel() != H * W:
-                raise ValueError('image_metrics: the mask must have H*W entries')
-        if out is None:
-            out = torch.empty(4, dtype=torch.float64, device=d)
-        elif not (out.is_contiguous() and out.dtype == torch.float64 and out.device == d and tuple(out.shape) == (4,)):
-            raise ValueError('image_metrics: out must be a contiguous float64 (4,) tensor on the engine\'s device')
         p = ra_metrics_params(H=int(H), W=int(W), bg_brightness=float(bg), data_range=float(data_range), mse_over_rays=int(bool(mse_over_rays)),
                               crop_to_mask=int(mask is not None))
         check(self.lib.ra_image_metrics(self.ctx, C.byref(p), _ptr(pred), _ptr(gt), _ptr(pix), P, _ptr(mask), _ptr(out), self.stream), 'ra_image_metrics')
@@ -520,23 +540,8 @@ class Engine:
         two assembled images in [0, 1] as the reference's evaluator calls it (base_evaluator.py:50-69), and its five per-tap terms.
         mask: the images are first cropped to its bounding rectangle.  Below 31 in a dimension: six NaNs.  out: a contiguous float64
         (6,) device tensor to fill.  Nothing is read back and nothing synchronises.  Needs lpips_load()."""
-        d = self.device
-        pred, gt = _f32(pred.reshape(-1, 3), d), _f32(gt.reshape(-1, 3), d)
+        pred, gt, pix, mask, out = self._image_pair('lpips', pred, gt, H, W, pix, mask, out, 6)
         P = pred.shape[0]
-        if gt.shape[0] != P:
-            raise ValueError('lpips: pred and gt differ in size')
-        if pix is not None:
-            pix = pix.detach().to(device=d, dtype=torch.int64).reshape(-1).contiguous()
-            if pix.numel() != P:
-                raise ValueError('lpips: one pixel index per ray')
-        if mask is not None:
-            mask = mask.detach().to(device=d).reshape(-1).ne(0).to(torch.uint8).contiguous()
-            if mask.numel() != H * W:
-                raise ValueError('lpips: the mask must have H*W entries')
-        if out is None:
-            out = torch.empty(6, dtype=torch.float64, device=d)
-        elif not (out.is_contiguous() and out.dtype == torch.float64 and out.device == d and tuple(out.shape) == (6,)):
-            raise ValueError('lpips: out must be a contiguous float64 (6,) tensor on the engine\'s device')
         p = ra_metrics_params(H=int(H), W=int(W), bg_brightness=float(bg), data_range=1.0, mse_over_rays=0, crop_to_mask=int(mask is not None))
         check(self.lib.ra_lpips(self.ctx, C.byref(p), _ptr(pred), _ptr(gt), _ptr(pix), P, _ptr(mask), _ptr(out), self.stream), 'ra_lpips')
         return out
@@ -696,7 +701,7 @@ class Engine:
 
     def kernel_time(self, kind):
         """(ms, launches) of one kernel family since the last reset: 0 = fused distance query (K3, every width), 1 = full query (K4),
-        2 = the 8-wave K3 only (launches that fill the chip), 3 = the 2- / 4-wave K3."""
+        2 = the 8-wave K3 only (launches that fill the chip), 3 = the 2- / 4-wave K3, 4 = the compensated distance query (K3C / K3CC)."""
         ms, n = C.c_float(), C.c_int()
         check(self.lib.ra_get_kernel_time(self.ctx, int(kind), C.byref(ms), C.byref(n), self.stream), 'ra_get_kernel_time')
         return float(ms.value), int(n.value)
@@ -725,7 +730,7 @@ class Engine:
         o, d = _f32(o.reshape(-1, 3), dv), _f32(d.reshape(-1, 3), dv)
         n = o.shape[0]
         near, far = torch.empty(n, device=dv), torch.empty(n, device=dv)
-        bb = (C.c_float * 6)(*[float(v) for v in bbox6])
+        bb = _bbox6(bbox6)
         check(self.lib.ra_debug_aabb(self.ctx, _ptr(o), _ptr(d), n, bb, _ptr(near), _ptr(far), self.stream), 'ra_debug_aabb')
         return near, far
 
@@ -738,7 +743,7 @@ class Engine:
         n = surf.shape[0]
         L = c.env_h * c.env_w
         lvis, ldot = torch.empty(n, L, device=dv), torch.empty(n, L, device=dv)
-        bb = (C.c_float * 6)(*[float(v) for v in bbox6])
+        bb = _bbox6(bbox6)
         p = self.trace_params(lv, lv.dist_th, not c.no_dfss)
         check(self.lib.ra_debug_lvis(self.ctx, _ptr(surf), _ptr(norm), _ptr(acc), n, bb, C.byref(p), float(lv.near_offset), _ptr(lvis), _ptr(ldot),
                                      self.stream), 'ra_debug_lvis')
