@@ -634,6 +634,41 @@ int ra_lpips_features(ra_ctx* ctx, const float* img_dev, int H, int W, int tap, 
 /* output pixels (of both images together) per workgroup tile of the convolutions: the tests take their edge sizes from it */
 int ra_lpips_tile_m(void);
 
+/* ---- evaluation: exact point-to-mesh distance, the primitive of the reference's mesh evaluator (lib/evaluators/mesh_evaluator.py) ----
+ * and of its bvh_distance_queries / point_mesh_distance callers (base_network.py:417-427, sample_utils.py:681-724, mesh_utils.py:758-764).
+ * ra_mesh_create builds a flat box structure over the triangles on the stream — box of the finite faces' centroids, 30-bit Morton
+ * codes, one radix sort, leaves of ra_mesh_tile(0) face records that keep their original face id, leaf boxes, boxes of groups of
+ * ra_mesh_tile(1) leaves — and reads nothing back.  verts: DEVICE, n_verts x 3 fp32.  faces: HOST, n_faces x 3 int32, checked against
+ * [0, n_verts) before anything is launched; the mesh keeps its own copy of them and gathers the triangles into its own storage, so both
+ * arrays are the caller's again once the stream has passed the call.  A face with a non-finite vertex is dropped on the device and is
+ * never an answer.  The mesh belongs to the ctx: ra_mesh_destroy frees it (after a device synchronisation), ra_ctx_destroy frees those
+ * still alive.  A mesh is immutable.  ra_mesh_create and ra_mesh_closest share scratch of the ctx (the sort's keys and the order of the
+ * query points): the mesh calls of ONE ctx must be ordered with respect to each other — one stream, or streams the caller orders — as
+ * the calls that share the ctx's other scratch must.
+ * Errors: "null argument", "bad sizes" (n_verts < 1, n_faces < 1, n_faces > 2^24), "face index" (an index outside [0, n_verts)),
+ * "not a mesh of this ctx". */
+typedef struct ra_mesh ra_mesh;
+enum { RA_MESH_BRUTE = 1,       /* scan every face, no pruning: the in-arithmetic reference of the sweep */
+       RA_MESH_UNSORTED = 2 };  /* test and measurement hook: do not Morton-sort the query points internally (the same bits, slower) */
+int ra_mesh_create(ra_ctx* ctx, const float* verts_dev, int n_verts, const int* faces_host, int n_faces, ra_mesh** out, void* stream);
+int ra_mesh_destroy(ra_ctx* ctx, ra_mesh* mesh);
+/* Per point (pts: DEVICE n x 3 fp32) the closest point of the mesh, in fp32: closest (n x 3), d2 (n) = the squared length of
+ * p - closest as stored, face (n) = the ORIGINAL index of a face that attains d2, bary (n x 3) = the barycentrics of closest in that
+ * face, in the face's vertex order.  Any output may be NULL, not all four; n == 0 launches nothing and reads no pointer.
+ * Per triangle: Ericson's region method (Real-Time Collision Detection 5.1.5) with every product and sum a named fp32 operation and
+ * every division guarded; a degenerate face acts as its segment or point.  Among faces of equal fp32 d2 the lowest original index wins.
+ * The result is therefore a function of (point, mesh) alone: not of the leaf order, the pruning, the wave a point sits in, the order
+ * of the points or the launch shape — the default call and RA_MESH_BRUTE agree bit for bit.  Pruning uses conservative box bounds only
+ * and never discards a box whose bound equals a lane's best.
+ * A point with a non-finite coordinate: d2 = closest = bary = NaN, face = -1.  A mesh whose every face was dropped: d2 = +inf,
+ * face = -1, closest = bary = NaN for every finite point.
+ * Asynchronous on stream, no read-back, no float atomics; scratch is allocated on the first call of a size only.
+ * Errors: "null argument", "bad sizes" (n < 0, n >= 2^30), "unknown flag", "not a mesh of this ctx". */
+int ra_mesh_closest(ra_ctx* ctx, const ra_mesh* mesh, const float* pts_dev, int n, int flags, float* d2_dev, float* closest_dev,
+                    int* face_dev, float* bary_dev, void* stream);
+/* test hook: 0 faces per leaf, 1 leaves per group, 2 points up to which a query is never sorted — the tests take their edge sizes from it */
+int ra_mesh_tile(int which);
+
 /* ---- test hooks: stage outputs for the parity tests (tests/test_gpu_*.py); not used by renderers ---- */
 /* resd + sdf MLPs on given big-pose points: resd n x 3, sdf n, feat n x 256 (any may be NULL) */
 /* the current frame's key lights (ra_config.key_light_share): n_lights flags and every light's largest share of a probe's power */

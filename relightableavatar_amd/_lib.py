@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RA_LIB_PATH') or os.path.join(_HERE, 'librelightableavatar_hip.so')    # override: kernel experiments (tools/)
 _lib = None
 ABI_VERSION = 9          # RA_ABI_VERSION of include/relightableavatar.h
+RA_MESH_BRUTE, RA_MESH_UNSORTED = 1, 2      # flags of ra_mesh_closest
 
 
 class RaError(RuntimeError):
@@ -162,6 +163,10 @@ SYMBOLS = {
     'ra_lpips': (C.c_int, [C.c_void_p, C.POINTER(ra_metrics_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ra_lpips_features': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'ra_lpips_tile_m': (C.c_int, []),
+    'ra_mesh_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    'ra_mesh_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'ra_mesh_closest': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    'ra_mesh_tile': (C.c_int, [C.c_int]),
     'ra_gen_rays': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_float), C.c_void_p] + [C.c_void_p] * 5 +
                     [C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     'ra_debug_mlp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -511,6 +511,89 @@ int ra_lpips_features(ra_ctx* c, const float* img, int H, int W, int tap, float*
     return 0;
 }
 
+// ---- exact point-to-mesh distance (ra_mesh.hip) -------------------------------------------------
+int ra_mesh_tile(int which) { return which == 0 ? MESH_LEAF : which == 1 ? MESH_FAN : which == 2 ? MESH_SORT_MIN : 0; }
+
+// the scratch of a Morton sort of n items (a mesh build, the points of a query); grown on the first call of a size only
+static int mesh_sort_scratch(ra_ctx* c, int n, MeshBuild* b) {
+    int err = 0;
+    b->temp_bytes = mesh_sort_temp_bytes(n);
+    b->bb = c->buf<unsigned>("mesh_bb", 8, &err);
+    b->keys = c->buf<unsigned>("mesh_keys", n, &err);
+    b->keys_sorted = c->buf<unsigned>("mesh_keys_sorted", n, &err);
+    b->vals = c->buf<int>("mesh_vals", n, &err);
+    b->vals_sorted = c->buf<int>("mesh_vals_sorted", n, &err);
+    b->temp = c->buf<char>("mesh_tmp", b->temp_bytes + 16, &err);
+    return err;
+}
+
+static ra_mesh* find_mesh(ra_ctx* c, const ra_mesh* m) {
+    for (auto& p : c->meshes) if (p.get() == m) return p.get();
+    return nullptr;
+}
+
+int ra_mesh_create(ra_ctx* c, const float* verts, int n_verts, const int* faces, int n_faces, ra_mesh** out, void* stream) {
+    RA_CHECK(c && out, "ra_mesh_create: null argument");
+    RA_CHECK(n_verts >= 1 && n_faces >= 1 && n_faces <= MESH_MAX_FACES, "ra_mesh_create: bad sizes (n_verts >= 1, 1 <= n_faces <= 2^24)");
+    RA_CHECK(verts && faces, "ra_mesh_create: null argument (verts, faces)");
+    for (size_t k = 0; k < (size_t)n_faces * 3; ++k)
+        RA_CHECK(faces[k] >= 0 && faces[k] < n_verts, "ra_mesh_create: face index outside [0, n_verts)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    std::unique_ptr<ra_mesh> m(new ra_mesh());
+    m->faces.assign(faces, faces + (size_t)n_faces * 3);
+    MeshView& v = m->view;
+    v.n_faces = n_faces; v.n_leaves = mesh_leaf_count(n_faces); v.n_groups = mesh_group_count(v.n_leaves);
+    MeshBuild b{};
+    int err = mesh_sort_scratch(c, n_faces, &b);
+    b.faces = c->buf<int>("mesh_faces", (size_t)n_faces * 3, &err);
+    RA_CHECK(!err && !m->recs.ensure((size_t)v.n_leaves * MESH_LEAF * MESH_REC * 4) && !m->lbox.ensure((size_t)v.n_leaves * 24) && !m->gbox.ensure((size_t)v.n_groups * 24),
+             "ra_mesh_create: out of device memory");
+    v.recs = m->recs.as<float>(); v.lbox = m->lbox.as<float>(); v.gbox = m->gbox.as<float>();
+    RA_HIP(hipMemcpyAsync(b.faces, m->faces.data(), (size_t)n_faces * 12, hipMemcpyHostToDevice, s));      // from the mesh's own copy
+    RA_CHECK(launch_mesh_build(verts, b, v, m->recs.as<float>(), m->lbox.as<float>(), m->gbox.as<float>(), s) == 0, "ra_mesh_create: device sort failed");
+    RA_HIP(hipGetLastError());
+    *out = m.get();
+    c->meshes.push_back(std::move(m));
+    return 0;
+}
+
+int ra_mesh_destroy(ra_ctx* c, ra_mesh* mesh) {
+    RA_CHECK(c, "ra_mesh_destroy: null argument");
+    if (!mesh) return 0;
+    RA_CHECK(find_mesh(c, mesh), "ra_mesh_destroy: not a mesh of this ctx");
+    hipSetDevice(c->device);
+    hipDeviceSynchronize();      // queries and the upload of its faces may still be queued
+    for (auto it = c->meshes.begin(); it != c->meshes.end(); ++it)
+        if (it->get() == mesh) { c->meshes.erase(it); break; }
+    return 0;
+}
+
+int ra_mesh_closest(ra_ctx* c, const ra_mesh* mesh, const float* pts, int n, int flags, float* d2, float* closest, int* face, float* bary,
+                    void* stream) {
+    RA_CHECK(c && mesh, "ra_mesh_closest: null argument");
+    RA_CHECK(find_mesh(c, mesh), "ra_mesh_closest: not a mesh of this ctx");
+    RA_CHECK(n >= 0 && n < (1 << 30), "ra_mesh_closest: bad sizes");
+    RA_CHECK((flags & ~(RA_MESH_BRUTE | RA_MESH_UNSORTED)) == 0, "ra_mesh_closest: unknown flag");
+    if (n == 0) return 0;       // nothing to read or write: empty arrays have no address
+    RA_CHECK(pts && (d2 || closest || face || bary), "ra_mesh_closest: null argument (pts, or all four outputs)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    MeshQuery q{};
+    q.pts = pts; q.n = n; q.brute = (flags & RA_MESH_BRUTE) != 0; q.d2 = d2; q.closest = closest; q.face = face; q.bary = bary;
+    // neighbours in space share a wave, so a wave opens little more than one lane would; the answers do not depend on it.  The
+    // exhaustive scan opens everything anyway
+    if (!q.brute && !(flags & RA_MESH_UNSORTED) && n > MESH_SORT_MIN) {
+        MeshBuild b{};
+        RA_CHECK(!mesh_sort_scratch(c, n, &b), "ra_mesh_closest: out of device memory");
+        RA_CHECK(launch_mesh_sort_points(pts, n, b, s) == 0, "ra_mesh_closest: device sort failed");
+        q.perm = b.vals_sorted;
+    }
+    launch_mesh_closest(mesh->view, q, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
 static void inv3x3(const double* m, double* o) {
     const double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];
     const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);

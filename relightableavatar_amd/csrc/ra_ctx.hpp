@@ -1,6 +1,7 @@
 // The opaque context behind the C ABI: packed weights, frame state, scratch arenas, counters.
 #pragma once
 #include "ra_kernels.hpp"
+#include <memory>
 
 struct HostNets {
     GeoNet geo{};
@@ -66,6 +67,13 @@ struct HintSlot {
     std::vector<int> vals;
 };
 
+// A triangle mesh built for closest-point queries (ra_mesh_create, ra_mesh.hip): owned by its context (ra_ctx::meshes), immutable once built
+struct ra_mesh {
+    MeshView view{};
+    DevBuf recs, lbox, gbox;        // face records in leaf order, leaf boxes, group boxes
+    std::vector<int> faces;         // the caller's face array: staging of the upload, alive as long as the copy may be pending
+};
+
 // what a timed launch was (Timer, ra_get_kernel_time)
 enum TimerKind { T_K3_WIDE = 0, T_K4 = 1, T_K3_NARROW = 2, T_K3C = 3 };      // 8-wave K3, full query (K4 pair), narrow K3, K3C
 
@@ -95,6 +103,8 @@ struct ra_ctx {
     DevBuf lpips_arena;
     std::vector<float> lpips_host;
     bool lpips_loaded = false;
+    // closest-point meshes still alive (ra_mesh_create); freed with the context
+    std::vector<std::unique_ptr<ra_mesh>> meshes;
     // frame
     FrameState fr{};
     DevBuf fvertA, fpverts4, fbias_r0, fbias_r4, fbias_c3, fbvh_pts, fbvh_pairs, fbvh_order;

@@ -242,6 +242,41 @@ void launch_lpips(const LpipsIO& io, hipStream_t s);
 void launch_lpips_features(const LpipsIO& io, int tap, float* out, hipStream_t s);
 void lpips_feature_shape(int H, int W, int tap, int* C, int* h, int* w);
 
+// Exact closest point on a triangle mesh (ra_mesh.hip): a flat box structure over Morton-sorted faces, swept with wave-uniform control flow
+constexpr int MESH_LEAF = 32;                    // face records per leaf
+constexpr int MESH_FAN = 8;                      // leaves per group
+constexpr int MESH_REC = 12;                     // floats per face record: a.xyz b.xyz c.xyz, the original face id (int bits; -1: no face), 2 unused
+constexpr int MESH_MAX_FACES = 1 << 24;
+constexpr int MESH_SORT_MIN = 64;                // queries of at most one wave of points are never sorted
+struct MeshView {
+    const float* recs;      // n_leaves x MESH_LEAF records
+    const float* lbox;      // n_leaves x 6 (lo, hi): the leaf's valid faces, widened by the rounding of a computed closest point
+    const float* gbox;      // n_groups x 6
+    int n_faces, n_leaves, n_groups;
+};
+struct MeshBuild {          // scratch of one build, all on the device
+    int* faces;             // n_faces x 3
+    unsigned* bb;           // 6 words: the centroids' box as order-preserving integers
+    unsigned *keys, *keys_sorted;
+    int *vals, *vals_sorted;
+    void* temp;
+    size_t temp_bytes;
+};
+struct MeshQuery {
+    const float* pts;
+    int n, brute;
+    const int* perm;        // nullable: thread i answers point perm[i]
+    float *d2, *closest, *bary;
+    int* face;
+};
+inline int mesh_leaf_count(int n_faces) { return (n_faces + MESH_LEAF - 1) / MESH_LEAF; }
+inline int mesh_group_count(int n_leaves) { return (n_leaves + MESH_FAN - 1) / MESH_FAN; }
+size_t mesh_sort_temp_bytes(int n);
+int launch_mesh_build(const float* verts, const MeshBuild& b, const MeshView& m, float* recs, float* lbox, float* gbox, hipStream_t s);
+// Morton order of the query points (non-finite points last): perm[i] = caller index of the i-th point
+int launch_mesh_sort_points(const float* pts, int n, const MeshBuild& b, hipStream_t s);
+void launch_mesh_closest(const MeshView& m, const MeshQuery& q, hipStream_t s);
+
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot
 void launch_scatter_maps(const int* hit_idx, const int* hit_count, int P, int premultiply, const float* acc_full,

@@ -5,6 +5,7 @@ library) and the stream.  All arithmetic of the render path happens in the HIP l
 """
 import contextlib
 import ctypes as C
+import weakref
 
 import torch
 
@@ -69,6 +70,54 @@ class RaysPending:
         if self._mask_host is not None:
             out.mask_host = self._mask_host.bool()
         return out
+
+
+class Mesh:
+    """a triangle mesh built for closest-point queries (Engine.mesh).  It belongs to its engine's context: close() — or garbage
+    collection — releases it while the engine lives; once the engine is gone the context has freed it and the handle only refuses."""
+    WANT = ('d2', 'closest', 'face', 'bary')
+
+    def __init__(self, engine, handle, n_faces):
+        self._engine, self._handle, self.n_faces = weakref.ref(engine), handle, n_faces
+
+    def _live_engine(self):
+        eng = self._engine()
+        if eng is None or not eng.ctx.value:
+            raise _lib.RaError('Mesh: the engine that built this mesh is gone')
+        if not self._handle.value:
+            raise _lib.RaError('Mesh: closed')
+        return eng
+
+    def closest(self, points, want=WANT, brute=False, sort=True):
+        """points (n,3) -> dotdict of the wanted outputs on the device, all fp32 but face (int32): d2 (n,) squared distance, closest
+        (n,3), face (n,) original index of a face that attains d2 (the lowest among equals), bary (n,3) of closest in that face.
+        brute: scan every face (the same bits, slower).  sort=False: do not Morton-sort the points internally (the same bits;
+        measurement).  A non-finite point: NaN and face -1.  Nothing is read back."""
+        eng = self._live_engine()
+        want = tuple(want)
+        if not want or any(k not in self.WANT for k in want):
+            raise ValueError(f'Mesh.closest: want must be a non-empty subset of {self.WANT}')
+        d = eng.device
+        pts = _f32(points.reshape(-1, 3), d)
+        n = pts.shape[0]
+        out = dotdict()
+        for k in want:
+            out[k] = torch.empty((n,) if k in ('d2', 'face') else (n, 3), dtype=torch.int32 if k == 'face' else torch.float32, device=d)
+        flags = (_lib.RA_MESH_BRUTE if brute else 0) | (0 if sort else _lib.RA_MESH_UNSORTED)
+        check(eng.lib.ra_mesh_closest(eng.ctx, self._handle, _ptr(pts), n, flags, *[_ptr(out.get(k)) for k in self.WANT], eng.stream), 'ra_mesh_closest')
+        return out
+
+    def close(self):
+        eng = self._engine()
+        if self._handle.value and eng is not None and eng.ctx.value:
+            check(eng.lib.ra_mesh_destroy(eng.ctx, self._handle), 'ra_mesh_destroy')
+        self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Engine:
@@ -563,6 +612,18 @@ class Engine:
         out = torch.empty(lpips_weights.CONV_SHAPES[int(tap)][0], h, w, device=d)
         check(self.lib.ra_lpips_features(self.ctx, _ptr(img), H, W, int(tap), _ptr(out), self.stream), 'ra_lpips_features')
         return out
+
+    def mesh(self, verts, faces):
+        """verts (V,3) float, faces (F,3) integer -> a Mesh handle for closest-point queries (include/relightableavatar.h: ra_mesh_create).
+        The vertices go to the device as they are (a device tensor makes no round trip); the faces are checked on the host against
+        [0, V) before anything is launched, so faces on the device cost a read-back (and its wait) here: pass host faces where there
+        is a choice.  Otherwise asynchronous; the handle owns nothing of the caller's."""
+        verts = _f32(verts.reshape(-1, 3), self.device)
+        faces = faces.detach().to('cpu', torch.int32).reshape(-1, 3).contiguous()
+        handle = C.c_void_p()
+        check(self.lib.ra_mesh_create(self.ctx, _ptr(verts), verts.shape[0], C.c_void_p(faces.data_ptr()), faces.shape[0], C.byref(handle), self.stream),
+              'ra_mesh_create')
+        return Mesh(self, handle, faces.shape[0])
 
     # ------------------------------------------------------------------ measurement
     def counters(self) -> dotdict:
