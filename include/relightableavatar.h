@@ -669,6 +669,60 @@ int ra_mesh_closest(ra_ctx* ctx, const ra_mesh* mesh, const float* pts_dev, int 
 /* test hook: 0 faces per leaf, 1 leaves per group, 2 points up to which a query is never sorted — the tests take their edge sizes from it */
 int ra_mesh_tile(int which);
 
+/* ---- mesh extraction: the two steps the reference's mesh renderer leaves to mcubes and trimesh (mesh_renderer.py:74-84) ----
+ * ra_marching_cubes: classic marching cubes on a DEVICE volume of nx x ny x nz fp32 values, x slowest (what reshape gives), with the
+ * classic corner and edge numbering, 256-entry tables derived by rule (relightableavatar_amd/mcubes_tables.py) and linear
+ * interpolation.  A corner is below when v < iso, so a NaN counts as not below (and a vertex next to one is NaN); cells all of whose
+ * corners are on one side give nothing.  Each grid edge whose ends straddle iso carries exactly ONE vertex, owned by the lower of its
+ * two grid points; each cell is owned by its minimum corner.  A vertex is in index coordinates, fp32: the owning point's (x, y, z) with
+ * t = (iso - a) / (b - a) added along the edge's axis, a the value at the owning point, b at the other end, every step one rounded
+ * fp32 operation (sub, sub, div, add).  Vertices are ordered by (owning point's linear index, axis x < y < z), faces by (cell's
+ * minimum corner's linear index, order in the table); no atomic decides an index, so the output is a function of the volume alone,
+ * bit for bit.  Face normals (right-hand rule) point towards SMALLER volume values.
+ * Two calls.  verts_dev == faces_dev == NULL: the size query — classifies, sums, writes the two counts to *n_verts / *n_faces (HOST)
+ * and synchronises the stream once.  The next call with the same volume pointer, sizes and iso and arrays of n_verts x 3 fp32 /
+ * n_faces x 3 int32 (DEVICE; NULL allowed where the count is 0) writes the mesh, asynchronously, and uses the query up.  The volume
+ * must not change in between (if it does the mesh is wrong; nothing is written outside the arrays).
+ * Errors: "null argument", "bad sizes" (an axis below 2, more than 2^27 points), "bad iso", "no size query". */
+/* ra_sdf_volume: the scalar volume in front of marching cubes (mesh_renderer.py:42-72).  xs / ys / zs: DEVICE fp32 axis coordinates
+ * (the caller's torch.arange(lo, hi + vs, vs): nothing here re-derives arange's rounding); the grid point (x, y, z) is
+ * (xs[x], ys[y], zs[z]).  verts: DEVICE n_verts x 3 fp32, what the filter measures against (the template vertices for
+ * RA_VOLUME_CANONICAL / _TPOSE, the world vertices for _POSED).  Per point: the exact K (1..4) nearest vertices by an exhaustive scan,
+ * d2 = (dx^2 + dy^2) + dz^2; d_k = sqrt(d2_k), w_k = 1 / (d_k + 1e-8) normalised; t = sum w_k d_k; kept when t < dist_th
+ * (sample_blend_K_closest_points without values, sample_utils.py:631-641, as mesh_renderer.py:44-46 calls it).
+ * A kept cell gets -sdf of the mode's decoder on the compensated (fp32-grade) tier — canonical: sdf(x); tpose: sdf(x + resd(x)), as
+ * ra_observed_sdf; posed: the hierarchical world query without the smooth transition, as ra_hdq_sdf(x, dist_th, 0) — every other
+ * cell and the pad get `fill`.  volume: DEVICE (nx + 2 pad) x (ny + 2 pad) x (nz + 2 pad) fp32, x slowest.  Needs weights and a frame.
+ * One blocking read-back (the kept count, also written to *n_kept when not NULL), then asynchronous.
+ * Errors: "null argument", "unknown mode", "bad sizes", "bad K", "bad dist_th or fill". */
+enum { RA_VOLUME_CANONICAL = 0, RA_VOLUME_TPOSE = 1, RA_VOLUME_POSED = 2 };
+int ra_sdf_volume(ra_ctx* ctx, const float* xs_dev, int nx, const float* ys_dev, int ny, const float* zs_dev, int nz, int mode,
+                  const float* verts_dev, int n_verts, int K, float dist_th, float fill, int pad, float* volume_dev, int* n_kept,
+                  void* stream);
+int ra_marching_cubes(ra_ctx* ctx, const float* volume_dev, int nx, int ny, int nz, float iso, float* verts_dev, int* faces_dev,
+                      int* n_verts, int* n_faces, void* stream);
+/* The largest component of a triangle mesh, components being sets of faces connected through SHARED EDGES (two faces that only share
+ * a vertex are not connected) — trimesh's split(only_watertight=False) followed by "the one with the most vertices".  Size = the
+ * number of distinct vertices the component's faces refer to; among equals the component that holds the lowest face index wins.  The
+ * result keeps the referenced vertices in their original order and the component's faces in their original order, re-indexed.
+ * Nothing else is done to the mesh: coincident vertices are not merged and degenerate faces are not dropped (trimesh.Trimesh's own
+ * processing is not reproduced).
+ * verts: DEVICE n_verts x 3 fp32, faces: DEVICE n_faces x 3 int32; both are checked on the device.  Two calls, as above: the size query
+ * (out_verts_dev == out_faces_dev == NULL) sorts the edges, lowers face labels to the component's lowest face index — integer minima
+ * only: the result does not depend on the order of execution — and reads the counts back ONCE: ra_mcubes_tile(1) label passes are
+ * queued together and decide on the device whether they still have work (a mesh that needs more gets another batch and another
+ * read-back; correct for any mesh); the second call gathers into out_verts_dev / out_faces_dev.  n_faces == 0: (0, 0).
+ * Errors: "null argument", "bad sizes", "face index" (an index outside [0, n_verts), reported by the size query), "no size query". */
+int ra_mesh_largest_component(ra_ctx* ctx, const float* verts_dev, int n_verts, const int* faces_dev, int n_faces, float* out_verts_dev,
+                              int* out_faces_dev, int* n_out_verts, int* n_out_faces, void* stream);
+/* test hook: 0 grid points / faces / edges per workgroup, 1 label passes queued per read-back of the component search, 2 vertices per
+ * LDS tile of the volume filter (= its workgroup size), 3 the largest K of the volume filter */
+int ra_mcubes_tile(int which);
+/* measurement hook: the blocking read-backs (stream synchronisations behind a device-to-host copy) that this ctx's last
+ * 0 ra_sdf_volume, 1 ra_marching_cubes size query, 2 ra_mesh_largest_component size query made, counted where they happen;
+ * 3 the label passes of that last component query that lowered a label; -1 for a null ctx */
+int ra_mesh_extract_stats(const ra_ctx* ctx, int which);
+
 /* ---- test hooks: stage outputs for the parity tests (tests/test_gpu_*.py); not used by renderers ---- */
 /* resd + sdf MLPs on given big-pose points: resd n x 3, sdf n, feat n x 256 (any may be NULL) */
 /* the current frame's key lights (ra_config.key_light_share): n_lights flags and every light's largest share of a probe's power */

@@ -36,6 +36,8 @@ UNSUPPORTED = {
     'geometry_normal': (False, 'part of render_bruteforce_human'),
     'geometry_visibility': (False, 'part of render_bruteforce_human'),
     'zero_roughness': (False, 'part of render_bruteforce_human'),
+    'mesh_simp_face': (-1, 'quadric decimation of the extracted mesh (mesh_renderer.py:95-96) needs open3d / trimesh'),
+    'track_tpose_mesh': (False, 'mesh tracking (lib/networks/renderer/mesh_tracker.py) is not mirrored'),
 }
 
 
@@ -123,6 +125,17 @@ def default_cfg() -> dotdict:
     c.vis_specular_map = False
     c.vis_novel_light = False
     c.vis_ground_shading = False
+    # mesh extraction (config.py:189,195,254,278,390-393; configs/base.yaml:98).  The three vis_*_mesh switches and track_tpose_mesh name
+    # files for visualizers.mesh_visualizer and select renderer.mesh_renderer in make_renderer
+    c.voxel_size = [0.005, 0.005, 0.005]
+    c.mesh_th = 0.5
+    c.mesh_th_to_sdf = False
+    c.mesh_simp_face = -1
+    c.surface_blend_weight = False
+    c.vis_tpose_mesh = False
+    c.vis_posed_mesh = False
+    c.vis_can_mesh = False
+    c.track_tpose_mesh = False
     # ground-plane pass (config.py:104-107, 45, 353; render_ground sphere_tracing_renderer.py:463-548)
     c.ground_normal = [0.0, 0.0, 1.0]
     c.ground_origin = [0.0, 0.0, 0.0]

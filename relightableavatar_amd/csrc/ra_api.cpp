@@ -126,8 +126,8 @@ FullIO full_io(ra_ctx* c) {
 
 // which distance queries run in compensated arithmetic (ra_config.trace_precision): the surface trace from 1 on, everything at 2
 // (the light-visibility rays towards the frame's key lights join them through hdq_pass's second fine list: ra_config.key_light_share)
-enum { Q_OTHER = 0, Q_SURFACE = 1 };
-static bool precise(const ra_ctx* c, int what) { return c->cfg.trace_precision >= 2 || (c->cfg.trace_precision == 1 && what == Q_SURFACE); }
+enum { Q_OTHER = 0, Q_SURFACE = 1, Q_PRECISE = 2 };      // Q_PRECISE: compensated whatever the configuration says (mesh extraction)
+static bool precise(const ra_ctx* c, int what) { return what == Q_PRECISE || c->cfg.trace_precision >= 2 || (c->cfg.trace_precision == 1 && what == Q_SURFACE); }
 static constexpr int KEY_LIGHTS_MAX = 48;       // per frame; bounds the second ray list of a light-visibility stage (rays <= pixels x this) and the tier's cost
 static bool key_tier(const ra_ctx* c) { return c->cfg.trace_precision == 1 && c->cfg.key_light_share > 0.f && c->n_lights > 0; }
 // the frame's key-light flags from the probe a render call shades with — unless the caller named the frame's probes itself (ra_set_key_probes)
@@ -259,6 +259,29 @@ static TraceState alloc_trace(ra_ctx* c, const std::string& p, int n, bool soft,
         ts.rlx = c->buf<float>(p + "rlx", n, err);
     }
     return ts;
+}
+
+// The decoders of mesh extraction (ra_sdf_volume) on n (or fewer: *count on the device) points, always on the compensated tier: a
+// vertex's position is a quotient of two neighbouring values.  mode 0: sdf(x), the canonical field — the distance query with
+// resd_limit 0, so that its residual head contributes tanh(z) * 0 and cpts = x exactly; 1: sdf(x + resd(x)), what ra_observed_sdf
+// computes; 2: the hierarchical query of world points without the smooth transition, what ra_hdq_sdf(smooth 0) computes.
+int sdf_points_precise(ra_ctx* c, int mode, const float* pts, int n, float dist_th, float* sdf, hipStream_t s) {
+    if (n <= 0) return 0;
+    if (mode == 2) {
+        RaySet rs{};
+        rs.mode = 0; rs.x = pts;
+        return hdq_pass(c, rs, n, dist_th, 0, sdf, s, Q_PRECISE);
+    }
+    int err = 0;
+    int* idx = c->buf<int>("fine_idx", n, &err);
+    if (err) return 1;
+    int* cnt = next_fine_counter(c, s);
+    launch_iota(idx, n, cnt, s);
+    MlpIO io{};
+    io.bpts = pts; io.idx = idx; io.count = cnt; io.sdf = sdf; io.dist_th = 1.f; io.smooth = 0;
+    io.resd_limit = mode == 0 ? 0.f : c->cfg.resd_limit; io.counters = dcnt(c);
+    fine_level(c, io, n, true, s);
+    return 0;
 }
 
 extern "C" {

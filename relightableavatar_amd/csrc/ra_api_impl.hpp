@@ -25,3 +25,5 @@ inline int raw_channels(const ra_ctx* c) { return c->cfg.relight ? 17 : 16; }
 FullIO full_io(ra_ctx* c);
 void k4_fwd_launch(ra_ctx* c, const FullIO& io, char* tape, hipStream_t s);
 int full_query(ra_ctx* c, FullIO io, int n, hipStream_t s);
+// the decoders of ra_sdf_volume (ra_api.cpp): mode 0 canonical sdf(x), 1 sdf(x + resd(x)), 2 the hierarchical query of world points; compensated tier
+int sdf_points_precise(ra_ctx* c, int mode, const float* pts, int n, float dist_th, float* sdf, hipStream_t s);

@@ -74,6 +74,24 @@ struct ra_mesh {
     std::vector<int> faces;         // the caller's face array: staging of the upload, alive as long as the copy may be pending
 };
 
+// The size query of ra_marching_cubes / ra_mesh_largest_component that the next writing call completes: what it was asked and what it
+// answered.  The offsets it computed stay in the context's scratch ("mc_*", "lcc_*") until then.
+struct McQuery {
+    const float* vol = nullptr;
+    int nx = 0, ny = 0, nz = 0;
+    float iso = 0.f;
+    int n_verts = 0, n_faces = 0;
+    int readbacks = 0;      // blocking read-backs of the last size query (ra_mesh_extract_stats)
+    bool valid = false;
+};
+struct LccQuery {
+    const float* verts = nullptr;
+    const int* faces = nullptr;
+    int n_verts = 0, n_faces = 0, out_verts = 0, out_faces = 0;
+    int readbacks = 0, passes = 0;      // of the last size query: blocking read-backs, label passes that lowered a label (ra_mesh_extract_stats)
+    bool valid = false;
+};
+
 // what a timed launch was (Timer, ra_get_kernel_time)
 enum TimerKind { T_K3_WIDE = 0, T_K4 = 1, T_K3_NARROW = 2, T_K3C = 3 };      // 8-wave K3, full query (K4 pair), narrow K3, K3C
 
@@ -105,6 +123,10 @@ struct ra_ctx {
     bool lpips_loaded = false;
     // closest-point meshes still alive (ra_mesh_create); freed with the context
     std::vector<std::unique_ptr<ra_mesh>> meshes;
+    // mesh extraction: the pending size queries (ra_marching_cubes, ra_mesh_largest_component)
+    int vol_readbacks = 0;      // blocking read-backs of the last ra_sdf_volume
+    McQuery mc_query;
+    LccQuery lcc_query;
     // frame
     FrameState fr{};
     DevBuf fvertA, fpverts4, fbias_r0, fbias_r4, fbias_c3, fbvh_pts, fbvh_pairs, fbvh_order;

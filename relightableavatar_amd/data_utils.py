@@ -6,6 +6,8 @@
                                                     get_rigid_transform (net_utils.py:1164-1183 / data_utils.py:1004-1069),
                                                     pose_points_to_tpose_points / tpose_points_to_pose_points / pose_points_to_world_points
                                                     (blend_utils.py:264-313), Meshes.verts_normals (pytorch3d, restated), get_bounds (:616-622)
+    mesh_grid_axes(bounds, voxel_size)              lib/datasets/mesh_dataset.py:46-48: the three aranges of the extraction grid
+    mesh_grid_pts(axes)                             :49, the reference's batch.pts
     DeviceFrameLoader                               pose_dataset.Dataset.__getitem__ (pose_dataset.py:45-113) for a camera + a pose
                                                     sequence: the §8b batch of one frame, assembled on the device
 
@@ -35,6 +37,18 @@ def get_blend(engine: Engine, poses, tjoints, parents, tverts, weights, big_A, f
     o = engine.pose_frame(poses, tjoints, parents, tverts, weights, big_A, faces, Rh, Th)
     return dotdict(A=o.A[None], joints=o.joints[None], pverts=o.pverts[None], wverts=o.wverts[None], pnorm=o.pnorm[None], R=o.R[None],
                    Th=o.Th.reshape(1, 1, 3), poses=o.poses[None], pbounds=o.pbounds[None], wbounds=o.wbounds[None], tpose_verts=o.tverts[None])
+
+
+def mesh_grid_axes(bounds, voxel_size):
+    """bounds (2,3), voxel_size (3,) -> (xs, ys, zs): the reference's own torch.arange(lo, hi + vs, vs) per axis, so that nothing
+    downstream re-derives arange's rounding (the number of points of an axis depends on it).  Host tensors, as the reference's."""
+    b = torch.as_tensor(np.asarray(bounds.detach().cpu() if isinstance(bounds, torch.Tensor) else bounds)).reshape(2, 3)
+    return tuple(torch.arange(b[0, k], b[1, k] + voxel_size[k], voxel_size[k]) for k in range(3))
+
+
+def mesh_grid_pts(axes):
+    """(nx,ny,nz,3) float32: the grid points of the three axes, x slowest"""
+    return torch.stack(torch.meshgrid(*axes, indexing='ij'), dim=-1).float()
 
 
 class DeviceFrameLoader:

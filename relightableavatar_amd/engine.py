@@ -625,6 +625,63 @@ class Engine:
               'ra_mesh_create')
         return Mesh(self, handle, faces.shape[0])
 
+    def sdf_volume(self, xs, ys, zs, mode, dist_th, fill=-10., pad=10, verts=None, K=None):
+        """the padded volume of -sdf for marching cubes (include/relightableavatar.h: ra_sdf_volume).  xs, ys, zs: the axis
+        coordinates (data_utils.mesh_grid_axes); mode 'canonical' | 'tpose' | 'posed'; verts (V,3): what the K-NN filter measures
+        against — default the current frame's template vertices, which is right for 'canonical' and 'tpose'; 'posed' needs the
+        world vertices (batch.wverts).  K: cfg.sample_vert_cnt.  Returns (nx + 2 pad, ny + 2 pad, nz + 2 pad) float32 on the device;
+        self.last_kept holds the kept points.  One blocking read-back."""
+        if mode not in _lib.RA_VOLUME_MODES:
+            raise ValueError(f'sdf_volume: mode must be one of {tuple(_lib.RA_VOLUME_MODES)}')
+        d = self.device
+        if verts is None:
+            if mode == 'posed' or self._frame_refs is None:
+                raise ValueError("sdf_volume: mode 'posed' needs verts= (the world vertices), the other modes a frame (set_frame)")
+            verts = self._frame_refs[self.FRAME_KEYS.index('tverts')]
+        verts = _f32(verts.reshape(-1, 3), d)
+        ax = [_f32(torch.as_tensor(a).reshape(-1), d) for a in (xs, ys, zs)]
+        pad = int(pad)
+        vol = torch.empty(tuple(a.numel() + 2 * pad for a in ax), dtype=torch.float32, device=d)
+        kept = C.c_int()
+        check(self.lib.ra_sdf_volume(self.ctx, _ptr(ax[0]), ax[0].numel(), _ptr(ax[1]), ax[1].numel(), _ptr(ax[2]), ax[2].numel(), _lib.RA_VOLUME_MODES[mode],
+                                     _ptr(verts), verts.shape[0], int(self.cfg.sample_vert_cnt if K is None else K), float(dist_th), float(fill), pad,
+                                     _ptr(vol), C.byref(kept), self.stream), 'ra_sdf_volume')
+        self.last_kept = kept.value
+        return vol
+
+    def marching_cubes(self, volume, iso):
+        """volume (nx,ny,nz) float -> (verts (V,3) float32 in index coordinates, faces (F,3) int32) on the device
+        (include/relightableavatar.h: ra_marching_cubes).  One blocking read-back: the two counts, to allocate the result."""
+        if volume.ndim != 3 or min(volume.shape) < 2:
+            raise ValueError('marching_cubes: volume must be (nx, ny, nz) with at least 2 points per axis')
+        d = self.device
+        vol = _f32(volume, d)
+        nx, ny, nz = (int(v) for v in vol.shape)
+        nv, nf = C.c_int(), C.c_int()
+        check(self.lib.ra_marching_cubes(self.ctx, _ptr(vol), nx, ny, nz, float(iso), None, None, C.byref(nv), C.byref(nf), self.stream), 'ra_marching_cubes')
+        verts = torch.empty(nv.value, 3, dtype=torch.float32, device=d)
+        faces = torch.empty(nf.value, 3, dtype=torch.int32, device=d)
+        if nv.value:        # a crossed edge has a cell with a triangle: faces too
+            check(self.lib.ra_marching_cubes(self.ctx, _ptr(vol), nx, ny, nz, float(iso), _ptr(verts), _ptr(faces), None, None, self.stream), 'ra_marching_cubes')
+        return verts, faces
+
+    def largest_component(self, verts, faces):
+        """verts (V,3) float, faces (F,3) integer -> (verts, faces) of the largest component of faces connected through shared edges, on
+        the device: the most vertices, then the lowest face index; referenced vertices and faces in their original order
+        (include/relightableavatar.h: ra_mesh_largest_component).  One blocking read-back unless the mesh needs more than
+        ra_mcubes_tile(1) label passes."""
+        d = self.device
+        v = _f32(verts.reshape(-1, 3), d)
+        f = faces.detach().to(device=d, dtype=torch.int32).reshape(-1, 3).contiguous()
+        nv, nf = C.c_int(), C.c_int()
+        args = (self.ctx, _ptr(v) if v.shape[0] else None, v.shape[0], _ptr(f) if f.shape[0] else None, f.shape[0])
+        check(self.lib.ra_mesh_largest_component(*args, None, None, C.byref(nv), C.byref(nf), self.stream), 'ra_mesh_largest_component')
+        ov = torch.empty(nv.value, 3, dtype=torch.float32, device=d)
+        of = torch.empty(nf.value, 3, dtype=torch.int32, device=d)
+        if nf.value:
+            check(self.lib.ra_mesh_largest_component(*args, _ptr(ov), _ptr(of), None, None, self.stream), 'ra_mesh_largest_component')
+        return ov, of
+
     # ------------------------------------------------------------------ measurement
     def counters(self) -> dotdict:
         c = ra_counters()

@@ -2,11 +2,12 @@
 
     bvh_distance(pts, verts, faces)                                   lib/utils/mesh_utils.py:758-764
     sample_closest_points_on_surface(points, verts, faces, values)    lib/utils/sample_utils.py:681-724
+    sample_blend_K_closest_points(src, ref, values, K)                lib/utils/sample_utils.py:631-646 (cast_knn_points :605-611)
     sample_surface(verts, faces, count, generator)                    trimesh.sample.sample_surface's method
     load_obj(path)                                                    what trimesh.load gives the mesh evaluator: vertices and faces
 
 The two distance functions take the engine that owns the HIP context (engine=, default: evaluators.mesh_evaluator.Evaluator.engine); they
-have no CPU fallback.  sample_surface and load_obj are plain torch / text and run anywhere.  Batches: the reference's signatures carry a
+have no CPU fallback.  sample_blend_K_closest_points, sample_surface and load_obj are plain torch / text and run anywhere.  Batches: the reference's signatures carry a
 batch dimension; B == 1 is supported, B > 1 is refused.
 """
 import torch
@@ -58,6 +59,34 @@ def sample_closest_points_on_surface(points: torch.Tensor, verts: torch.Tensor, 
     corners = faces[0].to(out.bary.device).long()[out.face.long().clamp_min(0)]       # (N,3); face -1 (a non-finite point) has NaN barycentrics
     interp = (values[corners] * out.bary[..., None].to(values.dtype)).sum(1)
     return interp.view(1, n, -1), out.d2.sqrt().view(1, n, 1)
+
+
+def sample_blend_K_closest_points(src: torch.Tensor, ref: torch.Tensor, values: torch.Tensor = None, K: int = 4, eps: float = 1e-8, chunk: int = 8192):
+    """src (1,N,3), ref (1,V,3), values (1,V,D) or None.  The exact K nearest points of ref per point of src (squared distances as
+    sum((p - v)^2), like pytorch3d's knn_points), their PLAIN distances d_k (the reference takes the square root first), weights
+    w_k = 1 / (d_k + eps) normalised to sum 1.  Without values: sum w_k d_k as (1,N,1); with values: (sum w_k values[k] (1,N,D), that
+    (1,N,1)).  Plain torch on src's device, in chunks of rows."""
+    if src.ndim != 3 or ref.ndim != 3:
+        raise ValueError('sample_blend_K_closest_points: src (B,N,3), ref (B,V,3)')
+    if src.shape[0] != 1 or ref.shape[0] != 1:
+        raise NotImplementedError('sample_blend_K_closest_points: batches with B > 1 are not supported')
+    p, v = src[0].float(), ref[0].float().to(src.device)
+    n = p.shape[0]
+    d2s, idxs = [], []
+    for i in range(0, max(n, 1), chunk):
+        q = p[i:i + chunk]
+        d2 = ((q[:, None, :] - v[None, :, :]) ** 2).sum(-1)
+        top = torch.topk(d2, K, dim=-1, largest=False, sorted=True)
+        d2s.append(top.values)
+        idxs.append(top.indices)
+    dists, idx = torch.cat(d2s).sqrt(), torch.cat(idxs)
+    w = 1 / (dists + eps)
+    w = w / w.sum(dim=-1, keepdim=True)
+    blended = (dists * w).sum(-1).view(1, n, 1)
+    if values is None:
+        return blended
+    values = values.reshape(-1, values.shape[-1]).to(src.device)
+    return torch.einsum('nkd,nk->nd', values[idx], w.to(values.dtype)).view(1, n, -1), blended
 
 
 def sample_surface(verts: torch.Tensor, faces: torch.Tensor, count: int, generator: torch.Generator = None):

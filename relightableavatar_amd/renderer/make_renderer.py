@@ -7,4 +7,6 @@ from .. import config
 def make_renderer(cfg, network):
     config.check_supported(cfg)
     config.set_active_cfg(cfg)
+    if cfg.get('vis_tpose_mesh', False) or cfg.get('vis_posed_mesh', False) or cfg.get('vis_can_mesh', False):       # config.py:507: mesh_cfg
+        return importlib.import_module('relightableavatar_amd.renderer.mesh_renderer').Renderer(network)
     return importlib.import_module(cfg.renderer_module).Renderer(network)
