@@ -668,6 +668,29 @@ int ra_mesh_closest(ra_ctx* ctx, const ra_mesh* mesh, const float* pts_dev, int 
                     int* face_dev, float* bary_dev, void* stream);
 /* test hook: 0 faces per leaf, 1 leaves per group, 2 points up to which a query is never sorted — the tests take their edge sizes from it */
 int ra_mesh_tile(int which);
+/* Per point (pts: DEVICE n x 3 fp32) the generalised winding number of the mesh (Jacobson et al. 2013; the reference's winding_number,
+ * lib/utils/mesh_utils.py:614-680): winding (n) = sum over every face the mesh kept of sign * Omega / (4 pi), fp32.  About 1 inside a
+ * closed mesh whose faces are wound outwards, 0 outside, and a smooth value in between near holes and open boundaries; a flipped face
+ * counts negative.  A face with a non-finite vertex was dropped at ra_mesh_create and contributes nothing.  Dense: every point sees
+ * every face (no tree, no approximation).
+ * Per pair (ra_winding_tri.hpp, every operation a named fp32 operation): u_i = (v_i - p) / |v_i - p|, sign = sign(det[u0 u1 u2]),
+ * Omega = 4 atan(sqrt(T + 1e-10)) with T = tan^2(Omega_0 / 4) — the reference's function, its eps included, evaluated through
+ * tan(Omega_0 / 4) = |det| / (hypot(det, den) + den), den = 1 + u0.u1 + u1.u2 + u2.u0, instead of its ill-conditioned L'Huilier
+ * product; det == 0 (a point in a face's plane, a face of no area) contributes exactly 0.
+ * The sum is carried in float64: faces in the mesh's stored order, in chunks of ra_winding_tile(1) records whose sums start from 0
+ * and are added in chunk order.  A point's result is therefore a function of (point, mesh) alone, bit for bit: not of n, of the order
+ * or the subset of the points, or of the launch shape — below ra_winding_tile(2) point tiles the faces are split across workgroups
+ * and a second pass adds the chunk sums in the same order (RA_WINDING_ONE_PASS / RA_WINDING_SPLIT force either shape: the same bits).
+ * NaN, as the reference's arithmetic gives it: a point with a non-finite coordinate, and a point bit-equal to a vertex of a kept face
+ * (0 / 0 in the normalisation).  No other point of the launch is affected.
+ * Asynchronous on stream, no read-back, no float atomics; n == 0 launches nothing and reads no pointer; scratch (the split launch's
+ * chunk sums) is allocated on the first call of a size only and belongs to the ctx: the ordering rule of the other mesh calls holds.
+ * Errors: "null argument", "bad sizes" (n < 0, n >= 2^30), "unknown flag", "not a mesh of this ctx". */
+enum { RA_WINDING_ONE_PASS = 1,   /* test and measurement hooks: every point sums all chunks itself ... */
+       RA_WINDING_SPLIT = 2 };    /* ... or one workgroup per (point tile, chunk) and the combining pass, whatever n is (both: "unknown flag") */
+int ra_mesh_winding(ra_ctx* ctx, const ra_mesh* mesh, const float* pts_dev, int n, int flags, float* winding_dev, void* stream);
+/* test hook: 0 points per tile (workgroup), 1 face records per chunk, 2 point tiles below which the faces are split across workgroups */
+int ra_winding_tile(int which);
 
 /* ---- mesh extraction: the two steps the reference's mesh renderer leaves to mcubes and trimesh (mesh_renderer.py:74-84) ----
  * ra_marching_cubes: classic marching cubes on a DEVICE volume of nx x ny x nz fp32 values, x slowest (what reshape gives), with the

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get('RA_LIB_PATH') or os.path.join(_HERE, 'librelightablea
 _lib = None
 ABI_VERSION = 9          # RA_ABI_VERSION of include/relightableavatar.h
 RA_MESH_BRUTE, RA_MESH_UNSORTED = 1, 2      # flags of ra_mesh_closest
+RA_WINDING_ONE_PASS, RA_WINDING_SPLIT = 1, 2      # flags of ra_mesh_winding
 RA_VOLUME_MODES = {'canonical': 0, 'tpose': 1, 'posed': 2}      # modes of ra_sdf_volume
 
 
@@ -168,6 +169,8 @@ SYMBOLS = {
     'ra_mesh_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
     'ra_mesh_closest': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'ra_mesh_tile': (C.c_int, [C.c_int]),
+    'ra_mesh_winding': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_winding_tile': (C.c_int, [C.c_int]),
     'ra_sdf_volume': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                 C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     'ra_marching_cubes': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),

@@ -595,6 +595,32 @@ int ra_mesh_closest(ra_ctx* c, const ra_mesh* mesh, const float* pts, int n, int
     return 0;
 }
 
+// ---- generalised winding number (ra_winding.hip) --------------------------------------------------
+int ra_winding_tile(int which) { return which == 0 ? WIND_BLOCK : which == 1 ? WIND_CHUNK : which == 2 ? WIND_SPLIT_TILES : 0; }
+
+int ra_mesh_winding(ra_ctx* c, const ra_mesh* mesh, const float* pts, int n, int flags, float* winding, void* stream) {
+    RA_CHECK(c && mesh, "ra_mesh_winding: null argument");
+    RA_CHECK(find_mesh(c, mesh), "ra_mesh_winding: not a mesh of this ctx");
+    RA_CHECK(n >= 0 && n < (1 << 30), "ra_mesh_winding: bad sizes");
+    RA_CHECK((flags & ~(RA_WINDING_ONE_PASS | RA_WINDING_SPLIT)) == 0 && flags != (RA_WINDING_ONE_PASS | RA_WINDING_SPLIT), "ra_mesh_winding: unknown flag");
+    if (n == 0) return 0;       // nothing to read or write: empty arrays have no address
+    RA_CHECK(pts && winding, "ra_mesh_winding: null argument (pts, winding)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    // few points: the faces are split across workgroups to fill the chip, and a second pass adds the chunk sums in chunk order (the same bits)
+    const long long n_chunks = wind_chunk_count(mesh->view.n_leaves), tiles = ((long long)n + WIND_BLOCK - 1) / WIND_BLOCK;
+    const bool split = (flags & RA_WINDING_SPLIT) || (!(flags & RA_WINDING_ONE_PASS) && n_chunks > 1 && tiles < WIND_SPLIT_TILES && n * n_chunks <= WIND_SPLIT_MAX);
+    double* partial = nullptr;
+    if (split) {
+        int err = 0;
+        partial = c->buf<double>("winding_partial", (size_t)(n * n_chunks), &err);
+        RA_CHECK(!err, "ra_mesh_winding: out of device memory");
+    }
+    launch_mesh_winding(mesh->view, pts, n, partial, winding, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- mesh extraction: marching cubes and the largest component (ra_mcubes.hip) -------------------
 int ra_mcubes_tile(int which) { return which == 0 ? MC_BLOCK : which == 1 ? LCC_PASSES : which == 2 ? VOL_TILE : which == 3 ? VOL_MAX_K : 0; }
 int ra_mesh_extract_stats(const ra_ctx* c, int which) {

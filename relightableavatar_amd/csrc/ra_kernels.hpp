@@ -277,6 +277,15 @@ int launch_mesh_build(const float* verts, const MeshBuild& b, const MeshView& m,
 int launch_mesh_sort_points(const float* pts, int n, const MeshBuild& b, hipStream_t s);
 void launch_mesh_closest(const MeshView& m, const MeshQuery& q, hipStream_t s);
 
+// Generalised winding number over a mesh's own face records (ra_winding.hip): one lane per point, faces summed in stored order
+constexpr int WIND_BLOCK = 64;                   // points per workgroup: one wave
+constexpr int WIND_CHUNK = 1024;                 // face records per chunk, a constant: a chunk's float64 sum starts from 0, chunk sums add in chunk order
+constexpr int WIND_SPLIT_TILES = 2048;           // fewer point tiles than this: one workgroup per (tile, chunk) and a combining pass ...
+constexpr long long WIND_SPLIT_MAX = 1ll << 24;  // ... as long as points x chunks float64 partial sums stay within this count (128 MiB)
+inline int wind_chunk_count(int n_leaves) { return (int)(((long long)n_leaves * MESH_LEAF + WIND_CHUNK - 1) / WIND_CHUNK); }
+// partial: nullptr = the one-pass kernel; else chunks x n float64 of scratch = the split launch (the same bits)
+void launch_mesh_winding(const MeshView& m, const float* pts, int n, double* partial, float* out, hipStream_t s);
+
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot
 void launch_scatter_maps(const int* hit_idx, const int* hit_count, int P, int premultiply, const float* acc_full,

@@ -107,6 +107,21 @@ class Mesh:
         check(eng.lib.ra_mesh_closest(eng.ctx, self._handle, _ptr(pts), n, flags, *[_ptr(out.get(k)) for k in self.WANT], eng.stream), 'ra_mesh_closest')
         return out
 
+    def winding(self, points, shape=None):
+        """points (n,3) -> (n,) float32 on the device: the generalised winding number of the mesh at every point (include/
+        relightableavatar.h: ra_mesh_winding), about 1 inside, 0 outside.  A function of (point, mesh) alone, bit for bit.  A non-finite
+        point and a point on a vertex: NaN.  shape: None lets the library choose the launch, 'one_pass' / 'split' force one (the same
+        bits; tests and measurement).  Nothing is read back."""
+        eng = self._live_engine()
+        if shape not in (None, 'one_pass', 'split'):
+            raise ValueError("Mesh.winding: shape must be None, 'one_pass' or 'split'")
+        pts = _f32(points.reshape(-1, 3), eng.device)
+        n = pts.shape[0]
+        out = torch.empty(n, dtype=torch.float32, device=eng.device)
+        flags = {None: 0, 'one_pass': _lib.RA_WINDING_ONE_PASS, 'split': _lib.RA_WINDING_SPLIT}[shape]
+        check(eng.lib.ra_mesh_winding(eng.ctx, self._handle, _ptr(pts), n, flags, _ptr(out), eng.stream), 'ra_mesh_winding')
+        return out
+
     def close(self):
         eng = self._engine()
         if self._handle.value and eng is not None and eng.ctx.value:

@@ -5,11 +5,26 @@
     sample_blend_K_closest_points(src, ref, values, K)                lib/utils/sample_utils.py:631-646 (cast_knn_points :605-611)
     sample_surface(verts, faces, count, generator)                    trimesh.sample.sample_surface's method
     load_obj(path)                                                    what trimesh.load gives the mesh evaluator: vertices and faces
+    winding_number(pts, verts, faces)                                 lib/utils/mesh_utils.py:614-680 (Mesh.winding: ra_mesh_winding)
+    winding_number_nooom(pts, verts, faces, quota_GB)                 :787-802 (the same call: the kernel materialises nothing)
+    winding_distance(pts, verts, faces, winding_th)                   :741-755
+    winding_distance_remesh(verts, faces, ...)                        :805-895
+    hierarchical_winding_distance_remesh(verts, faces, ...)           :767-784
+    sample_closest_points(src, ref, values)                           lib/utils/sample_utils.py:614-622
+    get_voxel_grid_and_update_bounds(voxel_size, bounds)              lib/utils/sample_utils.py:352-370
+    get_bounds(xyz, padding)                                          lib/utils/net_utils.py:1608-1616
 
-The two distance functions take the engine that owns the HIP context (engine=, default: evaluators.mesh_evaluator.Evaluator.engine); they
-have no CPU fallback.  sample_blend_K_closest_points, sample_surface and load_obj are plain torch / text and run anywhere.  Batches: the reference's signatures carry a
+The distance and winding functions take the engine that owns the HIP context (engine=, default: evaluators.mesh_evaluator.Evaluator.engine); they
+have no CPU fallback.  sample_blend_K_closest_points, sample_closest_points, the grid helpers, sample_surface and load_obj are plain torch / text and run anywhere.  Batches: the reference's signatures carry a
 batch dimension; B == 1 is supported, B > 1 is refused.
+
+The remesh keeps the reference's sequence (grid, vertex filter, surface filter, winding, shift x distance, -10 fill, marching cubes,
+largest component, scale) with Engine.marching_cubes and Engine.largest_component in the places of mcubes and trimesh.  Not kept, as in
+renderer/mesh_renderer.py: mcubes' vertex / face order and its winding — faces here are wound so that their
+right-hand normals point towards SMALLER volume values, which for this cube (positive inside) is outwards — and trimesh.Trimesh's
+merging of coincident vertices; the largest component is the one with the most vertices, the lowest face index among equals.
 """
+import numpy as np
 import torch
 
 
@@ -137,3 +152,150 @@ def load_obj(path):
     if int(f.min()) < 0 or int(f.max()) >= v.shape[0]:
         raise ValueError(f'{path}: a face index lies outside the {v.shape[0]} vertices')
     return v, f
+
+
+def sample_closest_points(src: torch.Tensor, ref: torch.Tensor, values: torch.Tensor = None, chunk: int = 8192):
+    """src (1,N,3), ref (1,V,3), values (1,V,D) or None: K = 1 of sample_blend_K_closest_points without the blending.  The PLAIN
+    distance to the nearest point of ref, (1,N,1); with values (the nearest point's values (1,N,D), that distance).  Plain torch on
+    src's device, in chunks of rows; the lowest index wins among equal distances."""
+    if src.ndim != 3 or ref.ndim != 3:
+        raise ValueError('sample_closest_points: src (B,N,3), ref (B,V,3)')
+    if src.shape[0] != 1 or ref.shape[0] != 1:
+        raise NotImplementedError('sample_closest_points: batches with B > 1 are not supported')
+    p, v = src[0].float(), ref[0].float().to(src.device)
+    n = p.shape[0]
+    d2s, idxs = [], []
+    for i in range(0, max(n, 1), chunk):
+        q = p[i:i + chunk]
+        low = ((q[:, None, :] - v[None, :, :]) ** 2).sum(-1).min(dim=-1)
+        d2s.append(low.values)
+        idxs.append(low.indices)
+    dists, idx = torch.cat(d2s).sqrt().view(1, n, 1), torch.cat(idxs)
+    if values is None:
+        return dists
+    values = values.reshape(-1, values.shape[-1]).to(src.device)
+    return values[idx].view(1, n, -1), dists
+
+
+def get_bounds(xyz: torch.Tensor, padding: float = 0.005) -> torch.Tensor:
+    """xyz (B,N,3) -> (B,2,3): the box of the points, widened by padding on every side"""
+    return torch.stack([xyz.min(dim=1)[0] - padding, xyz.max(dim=1)[0] + padding], dim=1)
+
+
+def get_voxel_grid_and_update_bounds(voxel_size, bounds: torch.Tensor):
+    """voxel_size [sx, sy, sz], bounds (B,2,3) -> (pts (B,X,Y,Z,3), bounds (B,2,3) of the grid that was made).  Per axis
+    torch.arange(lo, hi + size / 2, size) in bounds' dtype on bounds' device, from the bounds read to the host as the reference reads
+    them; the returned bounds are the first and the last grid point, which is what the voxel size then measures from."""
+    ret = []
+    for b in bounds:
+        ax = [torch.arange(b[0, k].item(), b[1, k].item() + voxel_size[k] / 2, voxel_size[k], dtype=b.dtype, device=b.device) for k in range(3)]
+        ret.append(torch.stack(torch.meshgrid(*ax, indexing='ij'), dim=-1))
+    pts = torch.stack(ret)
+    return pts, torch.stack([pts[:, 0, 0, 0], pts[:, -1, -1, -1]], dim=1)
+
+
+def _check_mesh_args(what, pts, verts, faces):
+    if (pts is not None and pts.ndim != 2) or verts.ndim != 2 or faces.ndim != 2:
+        raise ValueError(f'{what}: pts (N,3), verts (V,3), faces (F,3); batches are not supported')
+
+
+def winding_number(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, engine=None) -> torch.Tensor:
+    """pts (N,3), verts (V,3), faces (F,3) -> (N,) float32 on the device: the generalised winding number of the mesh at every point,
+    Mesh.winding of a mesh built for this call."""
+    _check_mesh_args('winding_number', pts, verts, faces)
+    mesh = _engine(engine).mesh(verts, faces)
+    try:
+        return mesh.winding(pts)
+    finally:
+        mesh.close()
+
+
+def winding_number_nooom(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, quota_GB: float = 15.0, engine=None) -> torch.Tensor:
+    """winding_number: the kernel holds one running sum per point, so there is nothing to chunk; the quota is accepted and unused"""
+    return winding_number(pts, verts, faces, engine=engine)
+
+
+def winding_shift(winding: torch.Tensor, level_set: float = 0.5, winding_th: float = 0.45) -> torch.Tensor:
+    """the reference's three lines (:750-752, :858-860): ((w - level_set) * 2).clip(-1, 1), then -1 below -1 + th and +1 above 1 - th, both strict"""
+    shift = ((winding - level_set) * 2).clip(-1, 1)
+    shift[shift < (-1 + winding_th)] = -1
+    shift[shift > (+1 - winding_th)] = +1
+    return shift
+
+
+def winding_distance(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, winding_th: float = 0.45, engine=None) -> torch.Tensor:
+    """pts (N,3) -> (N,) the signed distance to the mesh, positive INSIDE: the closest-point distance times the clamped winding sign.
+    One mesh is built and serves both queries."""
+    _check_mesh_args('winding_distance', pts, verts, faces)
+    mesh = _engine(engine).mesh(verts, faces)
+    try:
+        d = mesh.closest(pts, want=('d2',)).d2.sqrt()
+        return winding_shift(mesh.winding(pts), 0.5, winding_th) * d
+    finally:
+        mesh.close()
+
+
+def winding_distance_remesh(verts: torch.Tensor, faces: torch.Tensor, guide_verts: torch.Tensor = None, guide_faces: torch.Tensor = None,
+                            voxel_size=0.005, dist_th_verts=0.05, dist_th_tris=0.01, quota_GB=15.0, level_set=0.5, winding_th=0.75, engine=None,
+                            return_cube=False):
+    """A watertight remesh of a scan or an extracted mesh: marching cubes at 0 on the winding distance of a voxel grid around it.
+    verts (V,3), faces (F,3) -> (verts (V',3) in verts' dtype, faces (F',3) in faces' dtype) on the device.  The guide (default: the
+    mesh itself) only widens the two filters.  dist_th_verts should be no smaller than the longest edge or hole, dist_th_tris no
+    smaller than the widest hole.  quota_GB is accepted and unused.  return_cube: also the volume and the grid's bounds (2,3), for tests.
+    Blocking read-backs: the bounds of the grid, the two boolean filters, marching cubes' and the component search's counts."""
+    _check_mesh_args('winding_distance_remesh', None, verts, faces)
+    eng = _engine(engine)
+    dev = eng.device
+    own_guide = guide_verts is None or guide_faces is None
+    v32 = verts.detach().to(dev, torch.float32)
+    g32 = v32 if own_guide else guide_verts.detach().to(dev, torch.float32)
+    voxel_size, dist_th_verts, dist_th_tris = float(voxel_size), float(dist_th_verts), float(dist_th_tris)
+    wbounds = get_bounds(v32[None], dist_th_tris)
+    pts, wbounds = get_voxel_grid_and_update_bounds([voxel_size] * 3, wbounds)
+    sh = pts.shape[1:-1]
+    pts, wbounds = pts.view(-1, 3), wbounds[0]
+    # level 1: the distance to the nearest vertex
+    d1 = sample_closest_points(pts[None], v32[None])[0, ..., 0]
+    d0 = d1 if own_guide else sample_closest_points(pts[None], g32[None])[0, ..., 0]
+    close_verts = torch.minimum(d0, d1) < dist_th_verts
+    pts = pts[close_verts]
+    # level 2: the distance to the surface, then the winding number of what is left
+    mesh = eng.mesh(v32, faces)
+    try:
+        d1 = mesh.closest(pts, want=('d2',)).d2.sqrt()
+        if own_guide:
+            d0 = d1
+        else:
+            guide = eng.mesh(g32, guide_faces)
+            try:
+                d0 = guide.closest(pts, want=('d2',)).d2.sqrt()
+            finally:
+                guide.close()
+        close_tris = torch.minimum(d0, d1) < dist_th_tris
+        pts, d = pts[close_tris], d1[close_tris]
+        winding_d = winding_shift(mesh.winding(pts), level_set, winding_th) * d
+    finally:
+        mesh.close()
+    # undo the two filters: -10 (far outside) for everything they dropped
+    cube_tris = torch.full(close_tris.shape, -10.0, dtype=torch.float32, device=dev)
+    cube_tris[close_tris] = winding_d
+    cube_verts = torch.full(close_verts.shape, -10.0, dtype=torch.float32, device=dev)
+    cube_verts[close_verts] = cube_tris
+    cube = cube_verts.view(*sh)
+    v, f = eng.largest_component(*eng.marching_cubes(cube, 0.0))
+    v = (v * voxel_size + wbounds[0]).to(verts.dtype)
+    f = f.to(faces.dtype)
+    return (v, f, cube, wbounds) if return_cube else (v, f)
+
+
+def hierarchical_winding_distance_remesh(verts: torch.Tensor, faces: torch.Tensor, init_voxel_size=0.05, init_dist_th_verts=1.0, init_dist_th_tris=0.25,
+                                         steps=4, **kwargs):
+    """winding_distance_remesh over `steps` voxel sizes, each result guiding the next: the voxel size halves per step and both
+    thresholds shrink by decay = (dist_th_tris / (voxel_size / 2^(steps - 2)))^(1 / (steps - 1)), the reference's rule."""
+    guide_verts, guide_faces = verts, faces
+    voxel_size, dist_th_verts, dist_th_tris = init_voxel_size, init_dist_th_verts, init_dist_th_tris
+    decay = np.power(dist_th_tris / (voxel_size / 2 ** (steps - 2)), 1 / (steps - 1)) if steps > 1 else -1
+    for _ in range(int(steps)):
+        guide_verts, guide_faces = winding_distance_remesh(verts, faces, guide_verts, guide_faces, voxel_size, dist_th_verts, dist_th_tris, **kwargs)
+        voxel_size, dist_th_verts, dist_th_tris = voxel_size / 2, dist_th_verts / decay, dist_th_tris / decay
+    return guide_verts, guide_faces
