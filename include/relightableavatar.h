@@ -691,6 +691,39 @@ enum { RA_WINDING_ONE_PASS = 1,   /* test and measurement hooks: every point sum
 int ra_mesh_winding(ra_ctx* ctx, const ra_mesh* mesh, const float* pts_dev, int n, int flags, float* winding_dev, void* stream);
 /* test hook: 0 points per tile (workgroup), 1 face records per chunk, 2 point tiles below which the faces are split across workgroups */
 int ra_winding_tile(int which);
+/* Per ray (ray_o, ray_d: DEVICE n x 3 fp32; d is not normalised, t is in units of |d|) where it meets the mesh: the reference's
+ * moller_trumbore and ray_stabbing (lib/utils/mesh_utils.py:686-738) over the faces the mesh kept.
+ *   t (n)       the smallest t over the faces the hit predicate accepts; +inf without a hit
+ *   face (n)    the ORIGINAL index of a face that attains it, the lowest among faces of equal fp32 t; -1 without a hit
+ *   uv (n x 2)  that pair's u, v (hit point = (1 - u - v) a + u b + v c); NaN without a hit
+ *   count (n)   the number of faces the predicate accepts: the reference's inside.count_nonzero, whose parity is ray_stabbing
+ * Any output may be NULL, not all four; n == 0 launches nothing and reads no pointer.
+ * Per pair (ra_raycast_tri.hpp, every product, fused multiply-add and division a named fp32 operation): the reference's u, v, t, its
+ * eps included.  A pair is a hit when (1) the reference's two-sided test holds, t >= 0, u >= 0, v >= 0, u + v <= 1; (2) |det| is above
+ * the fp32 rounding bound of its own computation, 2^-21 sum_k |d_k| (|E1 x E2|_k with absolute products) — the grazing guard, the one
+ * departure from the reference, which below that bound "hits" faces the ray is nowhere near (a ray in a face's plane, a face of no area,
+ * d = 0); (3) the computed t lies in the computed ray interval of the face's own box, widened by 2^-6 relative: an exact hit does, and
+ * it is what makes the box sweep exact.  The test is not watertight on shared edges and vertices (u and v are rounded per face), and
+ * neither is the reference's: count may be off by one for a ray through an edge.
+ * The result is a function of (ray, mesh) alone, bit for bit: not of the leaf order, the pruning, the wave a ray sits in, the order or
+ * subset of the rays or the launch shape.  Boxes are pruned by a conservative slab test only; with count_dev given nothing is pruned
+ * by t.  The default call, RA_RAYCAST_BRUTE and RA_RAYCAST_UNSORTED agree bit for bit.
+ * A ray with a non-finite component of o or d: t = uv = NaN, face = -1, count = -1; no other ray is affected.  A mesh whose every
+ * face was dropped: t = +inf, face = -1, uv = NaN, count = 0.
+ * Asynchronous on stream, no read-back, no float atomics; scratch (the internal order of the rays) is allocated on the first call of
+ * a size only and belongs to the ctx: the ordering rule of the other mesh calls holds.
+ * Errors: "null argument", "bad sizes" (n < 0, n >= 2^30), "unknown flag", "not a mesh of this ctx". */
+enum { RA_RAYCAST_BRUTE = 1,      /* scan every face, no box test: the in-arithmetic reference of the sweep */
+       RA_RAYCAST_UNSORTED = 2 }; /* do not re-order the rays internally (the same bits; test and measurement hook) */
+int ra_mesh_raycast(ra_ctx* ctx, const ra_mesh* mesh, const float* ray_o_dev, const float* ray_d_dev, int n, int flags, float* t_dev,
+                    int* face_dev, float* uv_dev, int* count_dev, void* stream);
+/* test hook: 0 rays per workgroup, 1 pairs per workgroup of ra_ray_tri_pairs, 2 rays up to which a query is never re-ordered */
+int ra_raycast_tile(int which);
+/* The reference's dense moller_trumbore for tris of shape (f, 3, 3): u, v, t (each DEVICE n x f fp32, ray-major; any may be NULL, not
+ * all three) of every (ray, triangle) pair, raycast_tri with NO guard.  o, d: DEVICE n x 3; tris: DEVICE f x 9.  Needs no mesh.
+ * n == 0 or f == 0 launches nothing.  Errors: "null argument", "bad sizes" (n < 0, f < 0, n * f >= 2^31). */
+int ra_ray_tri_pairs(ra_ctx* ctx, const float* o_dev, const float* d_dev, int n, const float* tris_dev, int f, float* u_dev, float* v_dev,
+                     float* t_dev, void* stream);
 
 /* ---- mesh extraction: the two steps the reference's mesh renderer leaves to mcubes and trimesh (mesh_renderer.py:74-84) ----
  * ra_marching_cubes: classic marching cubes on a DEVICE volume of nx x ny x nz fp32 values, x slowest (what reshape gives), with the

@@ -13,6 +13,7 @@ _lib = None
 ABI_VERSION = 9          # RA_ABI_VERSION of include/relightableavatar.h
 RA_MESH_BRUTE, RA_MESH_UNSORTED = 1, 2      # flags of ra_mesh_closest
 RA_WINDING_ONE_PASS, RA_WINDING_SPLIT = 1, 2      # flags of ra_mesh_winding
+RA_RAYCAST_BRUTE, RA_RAYCAST_UNSORTED = 1, 2      # flags of ra_mesh_raycast
 RA_VOLUME_MODES = {'canonical': 0, 'tpose': 1, 'posed': 2}      # modes of ra_sdf_volume
 
 
@@ -171,6 +172,9 @@ SYMBOLS = {
     'ra_mesh_tile': (C.c_int, [C.c_int]),
     'ra_mesh_winding': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'ra_winding_tile': (C.c_int, [C.c_int]),
+    'ra_mesh_raycast': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    'ra_raycast_tile': (C.c_int, [C.c_int]),
+    'ra_ray_tri_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     'ra_sdf_volume': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                 C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     'ra_marching_cubes': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),

@@ -621,6 +621,45 @@ int ra_mesh_winding(ra_ctx* c, const ra_mesh* mesh, const float* pts, int n, int
     return 0;
 }
 
+// ---- ray-mesh intersection (ra_raycast.hip) -------------------------------------------------------
+int ra_raycast_tile(int which) { return which == 0 ? RAY_BLOCK : which == 1 ? RAY_PAIR_BLOCK : which == 2 ? MESH_SORT_MIN : 0; }
+
+int ra_mesh_raycast(ra_ctx* c, const ra_mesh* mesh, const float* ray_o, const float* ray_d, int n, int flags, float* t, int* face, float* uv,
+                    int* count, void* stream) {
+    RA_CHECK(c && mesh, "ra_mesh_raycast: null argument");
+    RA_CHECK(find_mesh(c, mesh), "ra_mesh_raycast: not a mesh of this ctx");
+    RA_CHECK(n >= 0 && n < (1 << 30), "ra_mesh_raycast: bad sizes");
+    RA_CHECK((flags & ~(RA_RAYCAST_BRUTE | RA_RAYCAST_UNSORTED)) == 0, "ra_mesh_raycast: unknown flag");
+    if (n == 0) return 0;       // nothing to read or write: empty arrays have no address
+    RA_CHECK(ray_o && ray_d && (t || face || uv || count), "ra_mesh_raycast: null argument (ray_o, ray_d, or all four outputs)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    RayQuery q{};
+    q.o = ray_o; q.d = ray_d; q.n = n; q.brute = (flags & RA_RAYCAST_BRUTE) != 0; q.t = t; q.face = face; q.uv = uv; q.count = count;
+    // rays whose origins are neighbours share a wave (the Morton order of ra_mesh_closest's points; equal origins keep their order:
+    // the radix sort is stable).  The answers do not depend on it
+    if (!q.brute && !(flags & RA_RAYCAST_UNSORTED) && n > MESH_SORT_MIN) {
+        MeshBuild b{};
+        RA_CHECK(!mesh_sort_scratch(c, n, &b), "ra_mesh_raycast: out of device memory");
+        RA_CHECK(launch_mesh_sort_points(ray_o, n, b, s) == 0, "ra_mesh_raycast: device sort failed");
+        q.perm = b.vals_sorted;
+    }
+    launch_mesh_raycast(mesh->view, q, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_ray_tri_pairs(ra_ctx* c, const float* o, const float* d, int n, const float* tris, int f, float* u, float* v, float* t, void* stream) {
+    RA_CHECK(c, "ra_ray_tri_pairs: null argument");
+    RA_CHECK(n >= 0 && f >= 0 && (long long)n * f < RAY_MAX_PAIRS, "ra_ray_tri_pairs: bad sizes (n >= 0, f >= 0, n * f < 2^31)");
+    if (n == 0 || f == 0) return 0;
+    RA_CHECK(o && d && tris && (u || v || t), "ra_ray_tri_pairs: null argument (o, d, tris, or all three outputs)");
+    RA_HIP(hipSetDevice(c->device));
+    launch_ray_tri_pairs(o, d, n, tris, f, u, v, t, (hipStream_t)stream);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- mesh extraction: marching cubes and the largest component (ra_mcubes.hip) -------------------
 int ra_mcubes_tile(int which) { return which == 0 ? MC_BLOCK : which == 1 ? LCC_PASSES : which == 2 ? VOL_TILE : which == 3 ? VOL_MAX_K : 0; }
 int ra_mesh_extract_stats(const ra_ctx* c, int which) {

@@ -286,6 +286,20 @@ inline int wind_chunk_count(int n_leaves) { return (int)(((long long)n_leaves * 
 // partial: nullptr = the one-pass kernel; else chunks x n float64 of scratch = the split launch (the same bits)
 void launch_mesh_winding(const MeshView& m, const float* pts, int n, double* partial, float* out, hipStream_t s);
 
+// Ray-mesh intersection over a mesh's box structure, and the dense ray x triangle pairs (ra_raycast.hip)
+constexpr int RAY_BLOCK = 64;                    // rays per workgroup: one wave
+constexpr int RAY_PAIR_BLOCK = 256;              // pairs per workgroup of the dense kernel
+constexpr long long RAY_MAX_PAIRS = 1ll << 31;   // the dense kernel answers fewer pairs than this
+struct RayQuery {
+    const float *o, *d;     // n x 3 each
+    int n, brute;
+    const int* perm;        // nullable: thread i answers ray perm[i]
+    float *t, *uv;          // nullable outputs; count != nullptr also turns the pruning by t off
+    int *face, *count;
+};
+void launch_mesh_raycast(const MeshView& m, const RayQuery& q, hipStream_t s);
+void launch_ray_tri_pairs(const float* o, const float* d, int n, const float* tris, int f, float* u, float* v, float* t, hipStream_t s);
+
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot
 void launch_scatter_maps(const int* hit_idx, const int* hit_count, int P, int premultiply, const float* acc_full,

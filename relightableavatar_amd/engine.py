@@ -122,6 +122,31 @@ class Mesh:
         check(eng.lib.ra_mesh_winding(eng.ctx, self._handle, _ptr(pts), n, flags, _ptr(out), eng.stream), 'ra_mesh_winding')
         return out
 
+    RAY_WANT = ('t', 'face', 'uv', 'count')
+
+    def raycast(self, ray_o, ray_d, want=RAY_WANT, brute=False, sort=True):
+        """ray_o, ray_d (n,3) -> dotdict of the wanted outputs on the device (include/relightableavatar.h: ra_mesh_raycast): t (n,)
+        fp32 the nearest hit in units of |ray_d| (+inf without one), face (n,) int32 the original index of the face hit (the lowest
+        among equal t; -1), uv (n,2) fp32 its barycentrics of b and c (NaN), count (n,) int32 the number of faces the ray meets (its
+        parity is the reference's ray_stabbing).  With count wanted nothing is pruned by t: ask for it only where it is used.
+        brute: test every face (the same bits, slower).  sort=False: do not re-order the rays internally (the same bits;
+        measurement).  A non-finite ray: NaN, face -1, count -1.  Nothing is read back."""
+        eng = self._live_engine()
+        want = tuple(want)
+        if not want or any(k not in self.RAY_WANT for k in want):
+            raise ValueError(f'Mesh.raycast: want must be a non-empty subset of {self.RAY_WANT}')
+        d = eng.device
+        o, r = _f32(ray_o.reshape(-1, 3), d), _f32(ray_d.reshape(-1, 3), d)
+        if o.shape != r.shape:
+            raise ValueError('Mesh.raycast: ray_o and ray_d must hold the same number of rays')
+        n = o.shape[0]
+        out = dotdict()
+        for k in want:
+            out[k] = torch.empty((n, 2) if k == 'uv' else (n,), dtype=torch.int32 if k in ('face', 'count') else torch.float32, device=d)
+        flags = (_lib.RA_RAYCAST_BRUTE if brute else 0) | (0 if sort else _lib.RA_RAYCAST_UNSORTED)
+        check(eng.lib.ra_mesh_raycast(eng.ctx, self._handle, _ptr(o), _ptr(r), n, flags, *[_ptr(out.get(k)) for k in self.RAY_WANT], eng.stream), 'ra_mesh_raycast')
+        return out
+
     def close(self):
         eng = self._engine()
         if self._handle.value and eng is not None and eng.ctx.value:
@@ -639,6 +664,20 @@ class Engine:
         check(self.lib.ra_mesh_create(self.ctx, _ptr(verts), verts.shape[0], C.c_void_p(faces.data_ptr()), faces.shape[0], C.byref(handle), self.stream),
               'ra_mesh_create')
         return Mesh(self, handle, faces.shape[0])
+
+    def ray_tri_pairs(self, ray_o, ray_d, tris):
+        """ray_o, ray_d (n,3), tris (F,3,3) -> (u, v, t), each (n,F) fp32 on the device: the reference's moller_trumbore for every
+        (ray, triangle) pair, no guard (include/relightableavatar.h: ra_ray_tri_pairs).  n x F must stay below 2^31."""
+        d = self.device
+        o, r, tr = _f32(ray_o.reshape(-1, 3), d), _f32(ray_d.reshape(-1, 3), d), _f32(tris.reshape(-1, 3, 3), d)
+        if o.shape != r.shape:
+            raise ValueError('ray_tri_pairs: ray_o and ray_d must hold the same number of rays')
+        n, f = o.shape[0], tr.shape[0]
+        if n * f >= 2 ** 31:
+            raise ValueError('ray_tri_pairs: n x F must stay below 2^31')
+        u, v, t = (torch.empty(n, f, dtype=torch.float32, device=d) for _ in range(3))
+        check(self.lib.ra_ray_tri_pairs(self.ctx, _ptr(o), _ptr(r), n, _ptr(tr), f, _ptr(u), _ptr(v), _ptr(t), self.stream), 'ra_ray_tri_pairs')
+        return u, v, t
 
     def sdf_volume(self, xs, ys, zs, mode, dist_th, fill=-10., pad=10, verts=None, K=None):
         """the padded volume of -sdf for marching cubes (include/relightableavatar.h: ra_sdf_volume).  xs, ys, zs: the axis

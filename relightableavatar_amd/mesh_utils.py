@@ -13,6 +13,9 @@
     sample_closest_points(src, ref, values)                           lib/utils/sample_utils.py:614-622
     get_voxel_grid_and_update_bounds(voxel_size, bounds)              lib/utils/sample_utils.py:352-370
     get_bounds(xyz, padding)                                          lib/utils/net_utils.py:1608-1616
+    moller_trumbore(ray_o, ray_d, tris)                               lib/utils/mesh_utils.py:710-738 (Engine.ray_tri_pairs: ra_ray_tri_pairs)
+    ray_stabbing(pts, verts, faces, multiplier, generator, ray_d)     :686-707 (Mesh.raycast: ra_mesh_raycast, count)
+    raycast_maps(ray_o, ray_d, verts, faces)                          acc / depth / normal maps of a mesh seen along given rays
 
 The distance and winding functions take the engine that owns the HIP context (engine=, default: evaluators.mesh_evaluator.Evaluator.engine); they
 have no CPU fallback.  sample_blend_K_closest_points, sample_closest_points, the grid helpers, sample_surface and load_obj are plain torch / text and run anywhere.  Batches: the reference's signatures carry a
@@ -208,6 +211,71 @@ def winding_number(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, 
         return mesh.winding(pts)
     finally:
         mesh.close()
+
+
+def moller_trumbore(ray_o: torch.Tensor, ray_d: torch.Tensor, tris: torch.Tensor, engine=None):
+    """ray_o, ray_d (n,3), tris (F,3,3) -> (u, v, t), each (n,F); with the reference's leading batch of 1 on all three — (1,n,3),
+    (1,n,3), (1,F,3,3) — each (1,n,F).  float32 on the device: the reference's u, v, t of every pair, its eps included, no guard."""
+    batched = ray_o.ndim == 3
+    if batched:
+        if ray_d.ndim != 3 or tris.ndim != 4:
+            raise ValueError('moller_trumbore: ray_o (B,n,3), ray_d (B,n,3), tris (B,F,3,3)')
+        if ray_o.shape[0] != 1 or ray_d.shape[0] != 1 or tris.shape[0] != 1:
+            raise NotImplementedError('moller_trumbore: batches with B > 1 are not supported')
+        ray_o, ray_d, tris = ray_o[0], ray_d[0], tris[0]
+    if ray_o.ndim != 2 or ray_d.shape != ray_o.shape or ray_o.shape[-1] != 3 or tris.ndim != 3 or tris.shape[1:] != (3, 3):
+        raise ValueError('moller_trumbore: ray_o (n,3), ray_d (n,3), tris (F,3,3)')
+    u, v, t = _engine(engine).ray_tri_pairs(ray_o, ray_d, tris)
+    return (u[None], v[None], t[None]) if batched else (u, v, t)
+
+
+def ray_stabbing(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, multiplier: int = 1, generator: torch.Generator = None,
+                 ray_d: torch.Tensor = None, engine=None) -> torch.Tensor:
+    """pts (n,3) -> (n,1) float32 on the device: the share of `multiplier` rays per point that cross the mesh an odd number of times
+    (1 inside a closed mesh, 0 outside), the reference's occupancy.  The directions are the reference's normalize(torch.rand_like(pts))
+    of the multiplier x n expanded points, drawn on pts' device with `generator`; with ray_d (multiplier * n, 3) given none is drawn.
+    A crossing is a face the hit predicate of ra_mesh_raycast accepts (its grazing guard included); a non-finite point counts -1,
+    odd."""
+    _check_mesh_args('ray_stabbing', pts, verts, faces)
+    n = pts.shape[0]
+    rep = pts[None].expand(multiplier, n, 3).reshape(-1, 3)
+    if ray_d is None:
+        ray_d = torch.rand(rep.shape, dtype=rep.dtype, device=rep.device, generator=generator)
+        ray_d = ray_d / ray_d.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    elif ray_d.shape != rep.shape:
+        raise ValueError(f'ray_stabbing: ray_d must be ({multiplier * n}, 3)')
+    mesh = _engine(engine).mesh(verts, faces)
+    try:
+        count = mesh.raycast(rep, ray_d, want=('count',)).count
+    finally:
+        mesh.close()
+    inside = (count % 2).bool().view(multiplier, n, -1)
+    return inside.sum(dim=0) / multiplier
+
+
+def raycast_maps(ray_o: torch.Tensor, ray_d: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, sort: bool = False, engine=None):
+    """ray_o, ray_d (..., 3) -> dotdict on the device, shaped like the rays: acc_map (..., 1) 1 where the ray meets the mesh, depth_map
+    (..., 1) t in units of |ray_d| (0 without a hit), norm_map (..., 3) the hit face's unit normal normalize((b - a) x (c - a)) (0
+    without a hit), face (...) int32 (-1).  Thin torch on Mesh.raycast: with the rays of Engine.gen_rays an extracted mesh is seen from
+    the dataset camera and compared with the sphere-traced acc and depth maps.  sort: Mesh.raycast's internal Morton order of the ray
+    origins; off by default, since a camera's rays leave one point in image order and the sort only costs there (DESIGN.md section 20);
+    the same bits either way."""
+    from .base_utils import dotdict
+    _check_mesh_args('raycast_maps', None, verts, faces)
+    eng = _engine(engine)
+    lead = ray_o.shape[:-1]
+    mesh = eng.mesh(verts, faces)
+    try:
+        hit = mesh.raycast(ray_o.reshape(-1, 3), ray_d.reshape(-1, 3), want=('t', 'face'), sort=sort)
+    finally:
+        mesh.close()
+    found = hit.face >= 0
+    tri = verts.to(device=hit.t.device, dtype=torch.float32)[faces.to(hit.t.device).long()[hit.face.long().clamp_min(0)]]        # (n,3,3)
+    nrm = torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    nrm = nrm / nrm.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+    zero = torch.zeros((), dtype=torch.float32, device=hit.t.device)
+    return dotdict(acc_map=found.float().view(*lead, 1), depth_map=torch.where(found, hit.t, zero).view(*lead, 1),
+                   norm_map=torch.where(found[:, None], nrm, zero).view(*lead, 3), face=hit.face.view(*lead))
 
 
 def winding_number_nooom(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, quota_GB: float = 15.0, engine=None) -> torch.Tensor:
