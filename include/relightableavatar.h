@@ -725,6 +725,80 @@ int ra_raycast_tile(int which);
 int ra_ray_tri_pairs(ra_ctx* ctx, const float* o_dev, const float* d_dev, int n, const float* tris_dev, int f, float* u_dev, float* v_dev,
                      float* t_dev, void* stream);
 
+/* ---- mesh connectivity and Taubin smoothing (lib/utils/mesh_utils.py: triangle_to_halfedge :540-611, get_edges :898-922,
+ * get_face_connectivity :146-168, laplacian_smoothing :943-1015) ----
+ * An ra_topo is the connectivity of n_faces triangles over n_verts vertices, built once on the device and immutable; it belongs to
+ * its ctx like an ra_mesh (freed by ra_topo_destroy or with the ctx) and holds no vertex positions.
+ * faces_dev: DEVICE n_faces x 3 int32 (what ra_marching_cubes writes), checked on the device against [0, n_verts).
+ * Conventions, the reference's: half-edge 3 f + k leaves corner k of face f towards corner (k + 1) % 3; an edge is the unordered pair
+ * of a half-edge's ends and its id is its rank in lexicographic (min, max) order; twin is the other half-edge of an edge that has
+ * exactly two, else -(the edge's number of half-edges).  The pairing is symmetric.  Arrays (ra_topo_array; all int32, DEVICE):
+ *   RA_TOPO_VERT, _TWIN, _EDGE   3 F each: start vertex, twin, edge id of every half-edge
+ *   RA_TOPO_EDGES                E x 2: the true (min, max) of every edge — NOT the reference's get_edges decode, which turns an edge
+ *                                (a, faces.max()) into (a + 1, 0)
+ *   RA_TOPO_EDGE_COUNTS          E: half-edges per edge (2 = manifold, 1 = boundary)
+ *   RA_TOPO_EDGE_HE_START, _HE   E + 1, 3 F: the half-edges of every edge, ascending (for a count of 2: the face connectivity)
+ *   RA_TOPO_NBR_START, _NBR      V + 1, 2 E: the neighbours of every vertex through the unique edges, ascending; an edge (a, a), which
+ *                                a face with a repeated index makes, lists a twice under a, as the reference's adjacency counts it
+ *   RA_TOPO_OUT_START, _OUT_HE   V + 1, 3 F: the half-edges that leave every vertex, ascending
+ * ra_topo_create queues everything and then reads back ONCE (the face-index verdict, E and the two largest valences together).
+ * n_faces == 0 gives an empty, valid object.  ra_topo_sizes (HOST, no device work): sizes[7] = F, V, E, the longest neighbour list,
+ * the most half-edges leaving one vertex, the blocking read-backs of the build, the most half-edges on one edge.  ra_topo_array copies one array to out_dev
+ * (asynchronous; an empty array may have out_dev == NULL).
+ * Errors: "null argument", "bad sizes", "face index" (outside [0, n_verts)), "not a topology of this ctx", "unknown array". */
+typedef struct ra_topo ra_topo;
+enum { RA_TOPO_VERT = 0, RA_TOPO_TWIN = 1, RA_TOPO_EDGE = 2, RA_TOPO_EDGES = 3, RA_TOPO_EDGE_COUNTS = 4, RA_TOPO_EDGE_HE_START = 5,
+       RA_TOPO_EDGE_HE = 6, RA_TOPO_NBR_START = 7, RA_TOPO_NBR = 8, RA_TOPO_OUT_START = 9, RA_TOPO_OUT_HE = 10 };
+int ra_topo_create(ra_ctx* ctx, const int* faces_dev, int n_faces, int n_verts, ra_topo** topo, void* stream);
+int ra_topo_destroy(ra_ctx* ctx, ra_topo* topo);
+int ra_topo_sizes(ra_ctx* ctx, const ra_topo* topo, int* sizes);
+int ra_topo_array(ra_ctx* ctx, const ra_topo* topo, int which, int* out_dev, void* stream);
+/* test hook: 0 half-edges / edges / vertices per workgroup of the build, 1 (vertex, channel) results per workgroup of a smoothing
+ * pass, 2 the largest channel count of ra_mesh_smooth */
+int ra_topo_tile(int which);
+/* Taubin lambda | mu smoothing of n_verts x C fp32 rows (positions; albedo, blend weights ... ride along as further channels),
+ * 1 <= C <= 64; the reference's laplacian_smoothing on the topology's true edges, float32.  An iteration is two passes; a pass is, per
+ * (vertex, channel) and in fp32 operations of one rounding each, no contraction (csrc/ra_topo_rules.hpp):
+ *     s = sum of the neighbour rows in ascending neighbour order, from 0;   l = s * inv - v   (inv = 1.0f / deg; 0 for deg = 0);
+ *     v' = v + c * l,   c = alpha in the first pass, -(alpha + 0.01f) in the second.
+ * Every pass reads the previous pass's buffer and writes another one (the reference's L @ v before +=): 2 x iters launches, no
+ * atomics, no read-back; the result is a function of the inputs alone, bit for bit.  inds_dev: DEVICE n_inds int64 row indices —
+ * only those rows move, every row is read (mesh_utils.py:1006, 1014); entries outside [0, n_verts) name no row; NULL: every row
+ * moves.  values_dev is not modified; out_dev (n_verts x C) must be another array.  iters == 0 copies.  A vertex without
+ * neighbours shrinks towards 0 like the reference's (l = -v).
+ * Errors: "null argument", "bad sizes", "bad alpha" (NaN), "not a topology of this ctx". */
+int ra_mesh_smooth(ra_ctx* ctx, const ra_topo* topo, const float* values_dev, int n_verts, int C, const long long* inds_dev, int n_inds,
+                   float alpha, int iters, float* out_dev, void* stream);
+/* One Loop subdivision step (halfedge_loop_subdivision, mesh_utils.py:382-514; export_mesh(..., subdivision=N) runs N of them):
+ * n_verts x C fp32 rows in, (n_verts + E) x C rows out (row V + e is the new vertex of edge e), 1 <= C <= 64 — positions, and albedo,
+ * roughness, blend weights ... carried along; the interior stencil sums to 1.  Every output row is the sum of its half-edges'
+ * contributions in ASCENDING half-edge order, each contribution in named fp32 operations of one rounding (csrc/ra_topo_rules.hpp,
+ * which states the four rules); the two coefficients per valence come from a table computed in double and rounded once to fp32
+ * (ra_loop_weights exposes an entry), which covers the topology's largest valence: the result is a function of the inputs alone,
+ * bit for bit.  The reference's quirks are kept: a boundary vertex of one face only gets half its stencil, an unreferenced vertex
+ * moves to the origin, a face with a repeated index runs through the same arithmetic.
+ * out_faces_dev (nullable): DEVICE 4 F x 3 int32 — face h < 3 F is (vert[h], V + edge[h], V + edge[prev h]), face 3 F + f holds the
+ * three edge vertices of face f.  *child (nullable): a new ra_topo of the subdivided mesh, owned by the ctx, made by the reference's
+ * index arithmetic on twin / vert / edge (:419-451): no sort, and no read-back, since E' = 2 E + 3 F is known.  Its edge ids are that
+ * arithmetic's (edge e splits into 2 e and 2 e + 1, the middle edge opposite half-edge h is 2 E + h), NOT lexicographic ranks;
+ * RA_TOPO_EDGES lists the ends of each id's lowest half-edge.  On an edge shared by three or more faces the two halves get their ids
+ * the opposite way round from the two directions, as in the reference, so an id there names half-edges of both halves: chained
+ * steps on such a mesh differ from a freshly built topology of the same faces; on closed and open manifold
+ * meshes they agree in every corner position.  Of the child's ra_topo_sizes the longest neighbour list is an upper bound.
+ * Without child the call synchronises the stream once when out_faces_dev is given (the faces are written through a temporary).
+ * Errors: "null argument", "bad sizes" (n_verts, C; a step whose 12 F half-edges or (V + E) x C values would leave int32),
+ * "not a topology of this ctx". */
+int ra_mesh_subdivide(ra_ctx* ctx, const ra_topo* topo, const float* values_dev, int n_verts, int C, float* out_values_dev, int* out_faces_dev,
+                      ra_topo** child, void* stream);
+/* test hook: the Loop coefficients of a vertex with n >= 1 outgoing half-edges, w_self = 1 / n - beta and
+ * beta = (1 / n)(5 / 8 - (3 / 8 + cos(2 pi / n) / 4)^2), as the library's table holds them (double, rounded once) */
+int ra_loop_weights(int n, float* w_self, float* beta);
+/* The vertex-mask dilation of segment_mesh (mesh_utils.py:226-236), (A^steps mask) != 0 as a neighbour-OR: after a step a vertex is
+ * set when one of its neighbours was (NOT when only itself was: the adjacency has no diagonal).  mask_dev, out_dev: DEVICE n_verts
+ * bytes, non-zero = set; out_dev holds 0 / 1 and must be another array; steps == 0 copies. */
+int ra_topo_dilate(ra_ctx* ctx, const ra_topo* topo, const unsigned char* mask_dev, int n_verts, int steps, unsigned char* out_dev,
+                   void* stream);
+
 /* ---- mesh extraction: the two steps the reference's mesh renderer leaves to mcubes and trimesh (mesh_renderer.py:74-84) ----
  * ra_marching_cubes: classic marching cubes on a DEVICE volume of nx x ny x nz fp32 values, x slowest (what reshape gives), with the
  * classic corner and edge numbering, 256-entry tables derived by rule (relightableavatar_amd/mcubes_tables.py) and linear

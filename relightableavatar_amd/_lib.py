@@ -14,6 +14,8 @@ ABI_VERSION = 9          # RA_ABI_VERSION of include/relightableavatar.h
 RA_MESH_BRUTE, RA_MESH_UNSORTED = 1, 2      # flags of ra_mesh_closest
 RA_WINDING_ONE_PASS, RA_WINDING_SPLIT = 1, 2      # flags of ra_mesh_winding
 RA_RAYCAST_BRUTE, RA_RAYCAST_UNSORTED = 1, 2      # flags of ra_mesh_raycast
+# the arrays of ra_topo_array, in the header's order
+RA_TOPO_ARRAYS = ('vert', 'twin', 'edge', 'edges', 'edge_counts', 'edge_he_start', 'edge_he', 'nbr_start', 'nbr', 'out_start', 'out_he')
 RA_VOLUME_MODES = {'canonical': 0, 'tpose': 1, 'posed': 2}      # modes of ra_sdf_volume
 
 
@@ -174,6 +176,15 @@ SYMBOLS = {
     'ra_winding_tile': (C.c_int, [C.c_int]),
     'ra_mesh_raycast': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'ra_raycast_tile': (C.c_int, [C.c_int]),
+    'ra_topo_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    'ra_topo_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'ra_topo_sizes': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    'ra_topo_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_topo_tile': (C.c_int, [C.c_int]),
+    'ra_mesh_smooth': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_mesh_subdivide': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    'ra_loop_weights': (C.c_int, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    'ra_topo_dilate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'ra_ray_tri_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     'ra_sdf_volume': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                 C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

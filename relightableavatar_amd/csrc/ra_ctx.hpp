@@ -74,6 +74,19 @@ struct ra_mesh {
     std::vector<int> faces;         // the caller's face array: staging of the upload, alive as long as the copy may be pending
 };
 
+// The connectivity of a triangle mesh (ra_topo_create, ra_topo.hip): owned by its context (ra_ctx::topos), immutable once built.  The
+// edge-sized arrays are allocated at their upper bound 3 n_faces, so that the build needs E only in its one read-back
+struct ra_topo {
+    TopoView view{};
+    int max_nbr = 0, max_out = 0;       // the longest neighbour list and the most half-edges that leave one vertex
+    int max_count = 0;                  // the most half-edges on one edge
+    int readbacks = 0;                  // blocking read-backs of the build
+    DevBuf vert, twin, edge, edges, counts, ehe_start, ehe, nbr_start, nbr, out_start, out_he;
+    // the Loop coefficients (w_self, beta) of every outgoing count 0..max_out (ra_topo_rules.hpp: loop_weights); host copy = staging
+    DevBuf loop_w;
+    std::vector<float> loop_w_host;
+};
+
 // The size query of ra_marching_cubes / ra_mesh_largest_component that the next writing call completes: what it was asked and what it
 // answered.  The offsets it computed stay in the context's scratch ("mc_*", "lcc_*") until then.
 struct McQuery {
@@ -123,6 +136,8 @@ struct ra_ctx {
     bool lpips_loaded = false;
     // closest-point meshes still alive (ra_mesh_create); freed with the context
     std::vector<std::unique_ptr<ra_mesh>> meshes;
+    // mesh connectivity still alive (ra_topo_create); freed with the context
+    std::vector<std::unique_ptr<ra_topo>> topos;
     // mesh extraction: the pending size queries (ra_marching_cubes, ra_mesh_largest_component)
     int vol_readbacks = 0;      // blocking read-backs of the last ra_sdf_volume
     McQuery mc_query;

@@ -300,6 +300,48 @@ struct RayQuery {
 void launch_mesh_raycast(const MeshView& m, const RayQuery& q, hipStream_t s);
 void launch_ray_tri_pairs(const float* o, const float* d, int n, const float* tris, int f, float* u, float* v, float* t, hipStream_t s);
 
+// Mesh connectivity and Taubin smoothing (ra_topo.hip)
+constexpr int TOPO_BLOCK = 256;                  // half-edges / edges / vertices per workgroup of the build kernels
+constexpr int TOPO_SMOOTH_BLOCK = 256;           // (vertex, channel) results per workgroup of the smoothing and dilation kernels
+constexpr int TOPO_MAX_FACES = (1 << 29) / 3;    // 3 F half-edges and their scratch stay far inside int32
+constexpr int TOPO_MAX_CHANNELS = 64;
+enum { TOPO_BAD = 0, TOPO_E = 1, TOPO_MAX_NBR = 2, TOPO_MAX_OUT = 3, TOPO_MAX_COUNT = 4, TOPO_STAT_INTS = 5 };      // the one read-back of a build
+struct TopoView {           // all device arrays, owned by the ra_topo; HE = 3 n_faces
+    int n_faces, n_verts, n_edges;
+    const int *vert, *twin, *edge;      // HE each
+    const int *edges, *counts;          // E x 2, E
+    const int *ehe_start, *ehe;         // E + 1, HE: the half-edges of an edge, ascending
+    const int *nbr_start, *nbr;         // V + 1, 2 E: the neighbours of a vertex, ascending
+    const int *out_start, *out_he;      // V + 1, HE: the half-edges that leave a vertex, ascending
+};
+struct TopoBuild {          // outputs (the ra_topo's buffers, E-sized ones at their upper bound HE) and the scratch of one build
+    const int* faces;
+    int n_faces, n_verts;
+    int *vert, *twin, *edge, *edges, *counts, *ehe_start, *ehe, *nbr_start, *nbr, *out_start, *out_he;
+    unsigned long long *keys, *keys_sorted;
+    int *slots, *head, *off, *deg, *odeg, *fill, *stat;
+    void* temp;
+    size_t temp_bytes;
+};
+size_t topo_temp_bytes(int n_faces, int n_verts);
+int launch_topo_build(const TopoBuild& b, hipStream_t s);
+// one Taubin pass: dst = src + c * (mean of the neighbours - src) on the rows with move[v] != 0 (move == nullptr: all), others copied
+void launch_topo_smooth_pass(const TopoView& t, const float* src, int C, const unsigned char* move, float c, float* dst, hipStream_t s);
+void launch_topo_mark_rows(const long long* inds, int n_inds, int n_verts, unsigned char* move, hipStream_t s);
+void launch_topo_dilate_pass(const TopoView& t, const unsigned char* src, unsigned char* dst, hipStream_t s);
+// one Loop step (ra_mesh_subdivide).  Positions: (V + E) x C rows from V x C, weights = the (w_self, beta) pairs per valence.
+void launch_loop_positions(const TopoView& t, const float* src, int C, const float* weights, float* dst, hipStream_t s);
+// The child's connectivity by index arithmetic: every array of `child` (sized for 4 F faces, V + E vertices, 2 E + 3 F edges) from the
+// parent's; faces_out (nullable) receives the 4 F x 3 faces.  deg (V' + 1, zero on entry), fill (V', zero on entry), scratch_stat
+// (TOPO_STAT_INTS) and temp are scratch.  No sort, no read-back.
+struct TopoChild {
+    int *vert, *twin, *edge, *edges, *counts, *ehe_start, *ehe, *nbr_start, *nbr, *out_start, *out_he;
+    int *deg, *fill, *scratch_stat;
+    void* temp;
+    size_t temp_bytes;
+};
+int launch_topo_child(const TopoView& t, const TopoChild& c, int* faces_out, hipStream_t s);
+
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot
 void launch_scatter_maps(const int* hit_idx, const int* hit_count, int P, int premultiply, const float* acc_full,

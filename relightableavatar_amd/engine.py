@@ -160,6 +160,128 @@ class Mesh:
             pass
 
 
+class Topology:
+    """the connectivity of a triangle mesh on the device (Engine.topology; include/relightableavatar.h: ra_topo_create): unique
+    edges, half-edges, vertex neighbours.  Immutable; holds no positions.  It belongs to its engine's context like a Mesh: close() — or
+    garbage collection — releases it while the engine lives; once the engine is gone the handle only refuses.  Arrays come back as
+    int64 tensors on the device, like the reference's, and are cached."""
+
+    def __init__(self, engine, handle):
+        self._engine, self._handle, self._cache = weakref.ref(engine), handle, {}
+        sizes = (C.c_int * 7)()
+        check(engine.lib.ra_topo_sizes(engine.ctx, handle, sizes), 'ra_topo_sizes')
+        self.F, self.V, self.E, self.max_valence, self.max_outgoing, self.readbacks, self.max_edge_count = (int(v) for v in sizes)
+        self.HE = 3 * self.F
+
+    def _live_engine(self):
+        eng = self._engine()
+        if eng is None or not eng.ctx.value:
+            raise _lib.RaError('Topology: the engine that built this topology is gone')
+        if not self._handle.value:
+            raise _lib.RaError('Topology: closed')
+        return eng
+
+    def array(self, name, dtype=torch.int64):
+        """one of _lib.RA_TOPO_ARRAYS as a device tensor (int32 is what the library holds; int64 is a cast)"""
+        key = (name, dtype)
+        if key not in self._cache:
+            eng = self._live_engine()
+            n = {'vert': self.HE, 'twin': self.HE, 'edge': self.HE, 'edges': 2 * self.E, 'edge_counts': self.E, 'edge_he_start': self.E + 1,
+                 'edge_he': self.HE, 'nbr_start': self.V + 1, 'nbr': 2 * self.E, 'out_start': self.V + 1, 'out_he': self.HE}[name]
+            out = torch.empty(n, dtype=torch.int32, device=eng.device)
+            check(eng.lib.ra_topo_array(eng.ctx, self._handle, _lib.RA_TOPO_ARRAYS.index(name), _ptr(out) if n else None, eng.stream), 'ra_topo_array')
+            self._cache[key] = out.to(dtype)
+        return self._cache[key]
+
+    @property
+    def edges(self):
+        """(E,2) the true (min, max) of every edge, lexicographic"""
+        return self.array('edges').view(-1, 2)
+
+    @property
+    def edge_counts(self):
+        """(E,) half-edges per edge: 2 manifold, 1 boundary"""
+        return self.array('edge_counts')
+
+    @property
+    def halfedge(self):
+        """the reference's triangle_to_halfedge structure without positions: twin, vert, edge (HE,), HE, E, F, V"""
+        return dotdict(verts=None, twin=self.array('twin'), vert=self.array('vert'), edge=self.array('edge'), HE=self.HE, E=self.E, F=self.F, V=self.V)
+
+    def face_connectivity(self):
+        """the reference's get_face_connectivity: (edges_connecting_faces (M,2), connected_faces (M,2)) over the M manifold edges in
+        edge order; within an edge the lower half-edge comes first (the reference leaves that order to an unstable argsort)."""
+        start, he = self.array('edge_he_start'), self.array('edge_he')
+        first = start[:-1][self.edge_counts == 2]
+        inds = torch.stack([he[first], he[first + 1]], dim=1) if first.numel() else torch.zeros(0, 2, dtype=torch.int64, device=he.device)
+        return self.array('vert')[inds], inds // 3
+
+    def smooth(self, values, inds=None, alpha=0.33, iter=90):
+        """Taubin smoothing of values (V,C) or (V,), 1 <= C <= 64 -> a new float32 tensor on the device (ra_mesh_smooth): the
+        reference's laplacian_smoothing on this topology's edges.  inds: integer indices or a bool mask of the rows that move."""
+        eng = self._live_engine()
+        v = _f32(values, eng.device)
+        if v.shape[:1] != (self.V,) or v.ndim > 2:
+            raise ValueError(f'Topology.smooth: values must be ({self.V}, C) or ({self.V},)')
+        if self.V == 0:
+            return v.clone()
+        v2 = v.reshape(self.V, -1)
+        out = torch.empty_like(v2)
+        ind = None
+        if inds is not None:
+            ind = torch.as_tensor(inds, device=eng.device)
+            ind = ind.nonzero(as_tuple=True)[0] if ind.dtype == torch.bool else ind.reshape(-1).to(torch.int64)
+            ind = torch.where(ind < 0, ind + self.V, ind).contiguous()
+        check(eng.lib.ra_mesh_smooth(eng.ctx, self._handle, _ptr(v2), self.V, v2.shape[1], _ptr(ind) if ind is not None and ind.numel() else None,
+                                     0 if ind is None else ind.numel(), float(alpha), int(iter), _ptr(out), eng.stream), 'ra_mesh_smooth')
+        if ind is not None and ind.numel() == 0:       # an empty selection moves nothing (a NULL list would move everything)
+            out.copy_(v2)
+        return out.reshape(v.shape)
+
+    def subdivide(self, values):
+        """one Loop subdivision step of values (V,C), 1 <= C <= 64 -> (values (V + E, C) float32, faces (4F, 3) int32, Topology of the
+        subdivided mesh), all on the device (ra_mesh_subdivide): the reference's halfedge_loop_subdivision.  Row V + e is the new
+        vertex of edge e.  The child comes from index arithmetic: nothing is sorted or read back."""
+        eng = self._live_engine()
+        v = _f32(values, eng.device)
+        if v.ndim != 2 or v.shape[0] != self.V or not 1 <= v.shape[1] <= 64:
+            raise ValueError(f'Topology.subdivide: values must be ({self.V}, C) with 1 <= C <= 64')
+        out = torch.empty(self.V + self.E, v.shape[1], dtype=torch.float32, device=eng.device)
+        faces = torch.empty(4 * self.F, 3, dtype=torch.int32, device=eng.device)
+        child = C.c_void_p()
+        check(eng.lib.ra_mesh_subdivide(eng.ctx, self._handle, _ptr(v) if v.numel() else None, self.V, v.shape[1], _ptr(out) if out.numel() else None,
+                                        _ptr(faces) if self.F else None, C.byref(child), eng.stream), 'ra_mesh_subdivide')
+        return out, faces, Topology(eng, child)
+
+    def dilate(self, mask, steps):
+        """mask (V,) bool -> bool: the vertex-mask dilation of the reference's segment_mesh, (A^steps mask) != 0; steps < 0 dilates
+        the complement, as there (ra_topo_dilate)."""
+        eng = self._live_engine()
+        m = torch.as_tensor(mask, device=eng.device).reshape(-1) != 0
+        if m.shape[0] != self.V:
+            raise ValueError(f'Topology.dilate: mask must hold {self.V} entries')
+        steps = int(steps)
+        if steps < 0:
+            m = ~m
+        src = m.to(torch.uint8).contiguous()
+        out = torch.empty_like(src)
+        check(eng.lib.ra_topo_dilate(eng.ctx, self._handle, _ptr(src), self.V, abs(steps), _ptr(out), eng.stream), 'ra_topo_dilate')
+        out = out != 0
+        return ~out if steps < 0 else out
+
+    def close(self):
+        eng = self._engine()
+        if self._handle.value and eng is not None and eng.ctx.value:
+            check(eng.lib.ra_topo_destroy(eng.ctx, self._handle), 'ra_topo_destroy')
+        self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     def __init__(self, cfg, device=None, relight=False):
         if not torch.cuda.is_available():
@@ -664,6 +786,15 @@ class Engine:
         check(self.lib.ra_mesh_create(self.ctx, _ptr(verts), verts.shape[0], C.c_void_p(faces.data_ptr()), faces.shape[0], C.byref(handle), self.stream),
               'ra_mesh_create')
         return Mesh(self, handle, faces.shape[0])
+
+    def topology(self, faces, n_verts):
+        """faces (F,3) integer, n_verts -> a Topology handle (include/relightableavatar.h: ra_topo_create).  Faces on the device make
+        no round trip (Engine.marching_cubes' int32 faces go in as they are) and are checked there against [0, n_verts).  One
+        blocking read-back."""
+        f = faces.detach().to(device=self.device, dtype=torch.int32).reshape(-1, 3).contiguous()
+        handle = C.c_void_p()
+        check(self.lib.ra_topo_create(self.ctx, _ptr(f) if f.shape[0] else None, f.shape[0], int(n_verts), C.byref(handle), self.stream), 'ra_topo_create')
+        return Topology(self, handle)
 
     def ray_tri_pairs(self, ray_o, ray_d, tris):
         """ray_o, ray_d (n,3), tris (F,3,3) -> (u, v, t), each (n,F) fp32 on the device: the reference's moller_trumbore for every

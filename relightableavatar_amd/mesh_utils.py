@@ -16,6 +16,12 @@
     moller_trumbore(ray_o, ray_d, tris)                               lib/utils/mesh_utils.py:710-738 (Engine.ray_tri_pairs: ra_ray_tri_pairs)
     ray_stabbing(pts, verts, faces, multiplier, generator, ray_d)     :686-707 (Mesh.raycast: ra_mesh_raycast, count)
     raycast_maps(ray_o, ray_d, verts, faces)                          acc / depth / normal maps of a mesh seen along given rays
+    get_edges(faces)                                                  :898-922 (Engine.topology: ra_topo_create; TRUE edges, see there)
+    laplacian_smoothing(v, e, inds, alpha, iter)                      :998-1015 (Topology.smooth: ra_mesh_smooth); returns a new tensor
+    triangle_to_halfedge(verts, faces)                                :540-611
+    halfedge_loop_subdivision / multiple_... / halfedge_to_triangle   :382-537 (Topology.subdivide: ra_mesh_subdivide)
+    loop_subdivision(v, f, steps)                                     :204-207
+    get_face_connectivity(faces)                                      :146-168
 
 The distance and winding functions take the engine that owns the HIP context (engine=, default: evaluators.mesh_evaluator.Evaluator.engine); they
 have no CPU fallback.  sample_blend_K_closest_points, sample_closest_points, the grid helpers, sample_surface and load_obj are plain torch / text and run anywhere.  Batches: the reference's signatures carry a
@@ -367,3 +373,86 @@ def hierarchical_winding_distance_remesh(verts: torch.Tensor, faces: torch.Tenso
         guide_verts, guide_faces = winding_distance_remesh(verts, faces, guide_verts, guide_faces, voxel_size, dist_th_verts, dist_th_tris, **kwargs)
         voxel_size, dist_th_verts, dist_th_tris = voxel_size / 2, dist_th_verts / decay, dist_th_tris / decay
     return guide_verts, guide_faces
+
+
+# ---------------------------------------------------------------------- connectivity and smoothing (Engine.topology: ra_topo_create)
+def _topology(faces: torch.Tensor, n_verts, engine):
+    if faces.ndim != 2 or faces.shape[-1] != 3 or faces.dtype.is_floating_point:
+        raise ValueError('mesh_utils: faces must be (F, 3) integers')
+    if n_verts is None:
+        n_verts = int(faces.max().item()) + 1 if faces.numel() else 0
+    return _engine(engine).topology(faces, n_verts)
+
+
+def get_edges(faces: torch.Tensor, engine=None):
+    """lib/utils/mesh_utils.py:898-922: (e (E,2), i (3F,), c (E,)) — the unique edges in lexicographic (min, max) order, every
+    half-edge's edge and every edge's number of half-edges, int64 on the device.  i and c are the reference's.  e holds the TRUE
+    (min, max): the one deliberate deviation.  The reference hashes with V = faces.max(), the largest index and not the count, and
+    decodes u // V, u % V, so an edge (a, faces.max()) comes back as (a + 1, 0), and its laplacian_smoothing fed those rows cuts the
+    last vertex loose.  e carries its topology: hand it to laplacian_smoothing as it is."""
+    topo = _topology(faces, None, engine)
+    e = topo.edges
+    e._ra_topology = topo
+    return e, topo.array('edge'), topo.edge_counts
+
+
+def laplacian_smoothing(v: torch.Tensor, e: torch.Tensor, inds: torch.Tensor = None, alpha=0.33, iter=90):
+    """lib/utils/mesh_utils.py:998-1015, Taubin lambda | mu smoothing in float32 (Topology.smooth: ra_mesh_smooth).  Returns a NEW
+    tensor (the reference also writes into v).  e must be the edge list get_edges returned, unchanged: the kernel runs on the topology
+    behind it, not on an arbitrary edge array."""
+    topo = getattr(e, '_ra_topology', None)
+    if topo is None:
+        raise ValueError('laplacian_smoothing: e must be the edge list that get_edges returned (it carries the device topology); '
+                         'an edited or re-built edge array is not accepted')
+    return topo.smooth(v, inds, alpha, iter)
+
+
+def triangle_to_halfedge(verts, faces: torch.Tensor, is_manifold: bool = False, engine=None):
+    """lib/utils/mesh_utils.py:540-611: dotdict(verts, twin, vert, edge, HE, E, F, V), int64 on the device, plus .topology, the
+    handle the arrays come from.  V is len(verts), or faces.max() without verts, as there.  is_manifold is accepted and ignored: the
+    general pairing gives the same twins on a manifold mesh."""
+    topo = _topology(faces, None if verts is None else len(verts), engine)
+    he = topo.halfedge
+    he.verts = verts
+    if verts is None:
+        he.V = topo.V - 1 if topo.V else 0
+    he.topology = topo
+    return he
+
+
+def get_face_connectivity(faces: torch.Tensor, engine=None):
+    """lib/utils/mesh_utils.py:146-168: (edges_connecting_faces (M,2), connected_faces (M,2)) over the manifold edges; the order
+    inside a pair, which the reference leaves to an unstable argsort, is ascending half-edge here."""
+    return _topology(faces, None, engine).face_connectivity()
+
+
+def halfedge_loop_subdivision(halfedge, is_manifold=False):
+    """lib/utils/mesh_utils.py:382-514: one Loop subdivision step of a structure that triangle_to_halfedge (or this function) returned
+    -> the next one, float32 positions (Topology.subdivide: ra_mesh_subdivide).  halfedge.verts may carry further channels (V, C).
+    is_manifold is accepted and ignored: boundary and non-manifold edges always get their own rules."""
+    topo = halfedge.get('topology')
+    if topo is None or halfedge.get('verts') is None:
+        raise ValueError('halfedge_loop_subdivision: needs the structure triangle_to_halfedge(verts, faces) returned (it carries the device topology)')
+    verts, _, child = topo.subdivide(halfedge.verts)
+    he = child.halfedge
+    he.verts = verts
+    he.topology = child
+    return he
+
+
+def multiple_halfedge_loop_subdivision(halfedge, steps=2, is_manifold=False):
+    """lib/utils/mesh_utils.py:517-520"""
+    for _ in range(steps):
+        halfedge = halfedge_loop_subdivision(halfedge, is_manifold)
+    return halfedge
+
+
+def halfedge_to_triangle(halfedge):
+    """lib/utils/mesh_utils.py:523-537: (verts, faces (F,3) int64) — the start vertices of every face's three half-edges"""
+    return halfedge.verts, halfedge.vert.view(-1, 3)
+
+
+def loop_subdivision(v: torch.Tensor, f: torch.Tensor, steps=2, engine=None):
+    """lib/utils/mesh_utils.py:204-207: `steps` Loop subdivision steps -> (verts float32, faces int64) on the device.  One
+    blocking read-back in all (the first topology's); the later levels come from index arithmetic."""
+    return halfedge_to_triangle(multiple_halfedge_loop_subdivision(triangle_to_halfedge(v, f, engine=engine), steps))

@@ -1,12 +1,13 @@
 """Writing an extracted mesh to disk (lib/visualizers/mesh_visualizer.py).
 
     Visualizer.visualize(output, batch)     :14-36: `<name>.npz` with every array of `output`, `<name>.ply` with the mesh
-    export_mesh(verts, faces, filename)     lib/utils/data_utils.py:251-265 for .ply and .npz, without trimesh
+    export_mesh(verts, faces, filename, subdivision)     lib/utils/data_utils.py:251-265 for .ply and .npz, without trimesh;
+                                            subdivision=N runs N Loop steps on the device first (mesh_utils.loop_subdivision)
 
 The file names follow the reference's rule: `can_mesh` for the canonical mesh (cfg.vis_can_mesh, or latent index -1 of a tracked
 T-pose mesh), else `<frame_index:04d>` under `track_mesh/`, `posed_mesh/` or `tpose_mesh/`.  The switches are read from the active
 cfg and default to False.  The .ply is binary little-endian: float32 x y z per vertex, then per face one uchar 3 and three int32.
-The reference's call of Blender afterwards (blend-weight replacement) is left out.  Plain numpy: runs anywhere.
+The reference's call of Blender afterwards (blend-weight replacement) is left out.  Without subdivision plain numpy: runs anywhere.
 """
 import os
 
@@ -38,7 +39,11 @@ def export_dotdict(output, filename):
     np.savez_compressed(filename, **arrays)
 
 
-def export_mesh(verts, faces, filename='default.ply'):
+def export_mesh(verts, faces, filename='default.ply', subdivision=0, engine=None):
+    if subdivision > 0:         # data_utils.py:252-254: Loop subdivision on the device (mesh_utils.loop_subdivision; needs the engine)
+        from ..mesh_utils import loop_subdivision
+        verts, faces = loop_subdivision(torch.as_tensor(_np(verts)) if not isinstance(verts, torch.Tensor) else verts,
+                                        torch.as_tensor(_np(faces)) if not isinstance(faces, torch.Tensor) else faces, subdivision, engine=engine)
     if filename.endswith('.npz'):
         export_dotdict(dict(verts=verts, faces=faces), filename)
     elif filename.endswith('.ply'):
