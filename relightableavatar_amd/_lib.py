@@ -185,6 +185,13 @@ SYMBOLS = {
     'ra_mesh_subdivide': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
     'ra_loop_weights': (C.c_int, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     'ra_topo_dilate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_topo_diffuse_apply': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    'ra_topo_diffuse_solve': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_double, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    'ra_mesh_normals': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    'ra_icp_residual': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 4),
+    'ra_adam_uniform_step': (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    'ra_fit_tile': (C.c_int, [C.c_int]),
     'ra_ray_tri_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     'ra_sdf_volume': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                 C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

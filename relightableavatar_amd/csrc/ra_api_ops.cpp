@@ -4,6 +4,7 @@
 #include "ra_api_impl.hpp"
 #include "ra_mcubes.hpp"
 #include "ra_topo_rules.hpp"
+#include "ra_fit_rules.hpp"
 #include <cmath>
 #include <cstring>
 
@@ -914,6 +915,115 @@ int ra_topo_dilate(ra_ctx* c, const ra_topo* topo, const unsigned char* mask, in
         launch_topo_dilate_pass(topo->view, src, dst, s);
         src = dst;
     }
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- mesh fitting: the large-steps operator and solve, normals, ICP residual, AdamUniform (ra_fit.hip) ----------------------------
+int ra_fit_tile(int which) { return which == 0 ? FIT_BLOCK : which == 1 ? FIT_BLOCK : 0; }
+
+int ra_topo_diffuse_apply(ra_ctx* c, const ra_topo* topo, const float* x, int n_verts, int C, float lambda, float* out, void* stream) {
+    RA_CHECK(c && topo, "ra_topo_diffuse_apply: null argument");
+    RA_CHECK(find_topo(c, topo), "ra_topo_diffuse_apply: not a topology of this ctx");
+    RA_CHECK(n_verts == topo->view.n_verts && C >= 1 && C <= FIT_MAX_CHANNELS, "ra_topo_diffuse_apply: bad sizes (n_verts of the topology, 1 <= C <= 64)");
+    RA_CHECK(lambda >= 0.0f && lambda <= 3.0e38f, "ra_topo_diffuse_apply: bad lambda (NaN, negative or infinite)");
+    if (n_verts == 0) return 0;
+    RA_CHECK(x && out && x != out, "ra_topo_diffuse_apply: null argument (x, out; out must not be x)");
+    RA_HIP(hipSetDevice(c->device));
+    launch_fit_apply(topo->view, x, C, (double)lambda, out, (hipStream_t)stream);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_topo_diffuse_solve(ra_ctx* c, const ra_topo* topo, const float* b, int n_verts, int C, float lambda, const float* x0, double tol, int max_iter,
+                          float* out, void* info, void* stream) {
+    RA_CHECK(c && topo, "ra_topo_diffuse_solve: null argument");
+    RA_CHECK(find_topo(c, topo), "ra_topo_diffuse_solve: not a topology of this ctx");
+    RA_CHECK(n_verts == topo->view.n_verts && C >= 1 && C <= FIT_MAX_CHANNELS && max_iter >= 0 && max_iter < (1 << 20),
+             "ra_topo_diffuse_solve: bad sizes (n_verts of the topology, 1 <= C <= 64, 0 <= max_iter < 2^20)");
+    RA_CHECK(lambda >= 0.0f && lambda <= 3.0e38f, "ra_topo_diffuse_solve: bad lambda (NaN, negative or infinite)");
+    RA_CHECK(tol >= 0.0 && tol < 1.0, "ra_topo_diffuse_solve: bad tol (0 <= tol < 1)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    if (n_verts == 0) {
+        if (info) RA_HIP(hipMemsetAsync(info, 0, (size_t)C * sizeof(FitInfo), s));
+        return 0;
+    }
+    RA_CHECK(b && out, "ra_topo_diffuse_solve: null argument (b, out)");
+    FitSolve f{};
+    f.nbr_start = topo->view.nbr_start; f.nbr = topo->view.nbr;
+    f.n_verts = n_verts; f.C = C; f.n_tiles = (n_verts + FIT_BLOCK - 1) / FIT_BLOCK;
+    f.b = b; f.x0 = x0; f.lambda = (double)lambda; f.tol = tol;
+    const size_t total = (size_t)n_verts * C;
+    int err = 0;
+    double* state = c->buf<double>("fit_state", 6 * total + n_verts, &err);
+    f.part = c->buf<double>("fit_part", (size_t)3 * C * f.n_tiles, &err);
+    f.st = c->buf<FitState>("fit_scalars", FIT_MAX_CHANNELS, &err);
+    RA_CHECK(!err, "ra_topo_diffuse_solve: out of device memory");
+    f.x = state; f.r = state + total; f.z = state + 2 * total; f.p0 = state + 3 * total; f.p1 = state + 4 * total; f.q = state + 5 * total; f.diag = state + 6 * total;
+    launch_fit_solve(f, max_iter, out, (FitInfo*)info, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_mesh_normals(ra_ctx* c, const ra_topo* topo, const float* verts, int n_verts, float* face_normal, float* face_area, float* vert_normal,
+                    void* stream) {
+    RA_CHECK(c && topo, "ra_mesh_normals: null argument");
+    RA_CHECK(find_topo(c, topo), "ra_mesh_normals: not a topology of this ctx");
+    RA_CHECK(n_verts == topo->view.n_verts, "ra_mesh_normals: bad sizes (n_verts of the topology)");
+    RA_CHECK(face_normal || face_area || vert_normal, "ra_mesh_normals: null argument (all three outputs)");
+    if (n_verts == 0) return 0;
+    RA_CHECK(verts, "ra_mesh_normals: null argument (verts)");
+    RA_HIP(hipSetDevice(c->device));
+    launch_mesh_normals(topo->view, verts, face_normal, face_area, vert_normal, (hipStream_t)stream);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_icp_residual(ra_ctx* c, const ra_mesh* mesh, const float* pts, const float* pt_normals, int n, const float* face_normals, float dist_th,
+                    float angle_th, double* sums, float* grad, unsigned char* keep, void* stream) {
+    RA_CHECK(c && mesh && sums, "ra_icp_residual: null argument");
+    RA_CHECK(find_mesh(c, mesh), "ra_icp_residual: not a mesh of this ctx");
+    RA_CHECK(n >= 0 && n < (1 << 29), "ra_icp_residual: bad sizes");
+    RA_CHECK(dist_th == dist_th && angle_th == angle_th, "ra_icp_residual: bad threshold (NaN)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    if (n == 0) {       // an empty mean: sum 0 over count 0
+        RA_HIP(hipMemsetAsync(sums, 0, 2 * sizeof(double), s));
+        return 0;
+    }
+    RA_CHECK(pts && pt_normals && face_normals, "ra_icp_residual: null argument (pts, pt_normals, face_normals)");
+    IcpJob j{};
+    j.n = n; j.n_faces = mesh->view.n_faces; j.n_tiles = (n + FIT_BLOCK - 1) / FIT_BLOCK;
+    j.pts = pts; j.pt_normals = pt_normals; j.face_normals = face_normals; j.dist_th = dist_th; j.angle_th = angle_th;
+    int err = 0;
+    float* d2 = c->buf<float>("icp_d2", n, &err);
+    float* closest = c->buf<float>("icp_closest", (size_t)n * 3, &err);
+    int* face = c->buf<int>("icp_face", n, &err);
+    j.part = c->buf<double>("icp_part", (size_t)2 * j.n_tiles, &err);
+    j.keep = keep ? keep : c->buf<unsigned char>("icp_keep", n, &err);
+    RA_CHECK(!err, "ra_icp_residual: out of device memory");
+    if (ra_mesh_closest(c, mesh, pts, n, 0, d2, closest, face, nullptr, stream)) return 1;
+    j.d2 = d2; j.closest = closest; j.face = face;
+    launch_icp_residual(j, sums, grad, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_adam_uniform_step(ra_ctx* c, float* param, const float* grad, float* g1, float* g2, long long n, int step, float lr, float b1, float b2,
+                         void* stream) {
+    RA_CHECK(c, "ra_adam_uniform_step: null argument");
+    RA_CHECK(n >= 0 && n < (1ll << 31) && step >= 1 && step < (1 << 24), "ra_adam_uniform_step: bad sizes (0 <= n < 2^31, 1 <= step < 2^24)");
+    RA_CHECK(lr == lr && b1 >= 0.0f && b1 < 1.0f && b2 >= 0.0f && b2 < 1.0f, "ra_adam_uniform_step: bad lr or betas (0 <= beta < 1)");
+    if (n == 0) return 0;
+    RA_CHECK(param && grad && g1 && g2, "ra_adam_uniform_step: null argument (param, grad, g1, g2)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    int err = 0;
+    unsigned* scratch = c->buf<unsigned>("adam_scratch", 2, &err);
+    RA_CHECK(!err, "ra_adam_uniform_step: out of device memory");
+    RA_HIP(hipMemsetAsync(scratch, 0, 2 * sizeof(unsigned), s));
+    launch_adam_uniform(param, grad, g1, g2, n, scratch, (double)lr, (double)b1, (double)b2, 1.0 - fit_pow((double)b1, step), 1.0 - fit_pow((double)b2, step), s);
     RA_HIP(hipGetLastError());
     return 0;
 }

@@ -342,6 +342,38 @@ struct TopoChild {
 };
 int launch_topo_child(const TopoView& t, const TopoChild& c, int* faces_out, hipStream_t s);
 
+// Mesh fitting (ra_fit.hip): the operator M = I + lambda L on a topology's neighbour lists and its conjugate-gradient solve, normals, the
+// ICP residual, the AdamUniform step
+constexpr int FIT_BLOCK = 256;                   // vertices of one channel per workgroup of the solve; rows per workgroup of the residual
+constexpr int FIT_MAX_CHANNELS = TOPO_MAX_CHANNELS;
+enum { FIT_STOP_NONE = 0, FIT_STOP_CONVERGED = 1, FIT_STOP_ZERO = 2, FIT_STOP_NAN = 3, FIT_STOP_BREAKDOWN = 4 };
+struct FitState { double rz, alpha, beta, bb, relres; int stop, iters; };      // of one channel, on the device
+struct FitInfo { int iters, stop; double relres; };                            // what ra_topo_diffuse_solve reports per channel
+struct FitSolve {
+    const int *nbr_start, *nbr;
+    int n_verts, C, n_tiles;        // n_tiles = workgroups per channel
+    const float *b, *x0;            // x0 nullable: 0
+    double lambda, tol;
+    double *x, *r, *z, *p0, *p1, *q;        // C x n_verts each (channel-major)
+    double* diag;                   // n_verts: M's diagonal, the Jacobi preconditioner
+    double* part;                   // 3 x C x n_tiles partial sums
+    FitState* st;                   // C
+};
+struct IcpJob {
+    const float *pts, *pt_normals, *face_normals, *d2, *closest;
+    const int* face;
+    int n, n_faces, n_tiles;
+    float dist_th, angle_th;
+    unsigned char* keep;            // n
+    double* part;                   // 2 x n_tiles
+};
+void launch_fit_apply(const TopoView& t, const float* x, int C, double lambda, float* out, hipStream_t s);
+void launch_fit_solve(const FitSolve& f, int max_iter, float* out, FitInfo* info, hipStream_t s);
+void launch_mesh_normals(const TopoView& t, const float* verts, float* fn, float* area, float* vn, hipStream_t s);
+void launch_icp_residual(const IcpJob& j, double* sums, float* grad, hipStream_t s);
+void launch_adam_uniform(float* param, const float* grad, float* g1, float* g2, long long n, unsigned* scratch, double lr, double b1, double b2, double c1,
+                         double c2, hipStream_t s);
+
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot
 void launch_scatter_maps(const int* hit_idx, const int* hit_count, int P, int premultiply, const float* acc_full,

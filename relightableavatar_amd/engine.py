@@ -147,6 +147,29 @@ class Mesh:
         check(eng.lib.ra_mesh_raycast(eng.ctx, self._handle, _ptr(o), _ptr(r), n, flags, *[_ptr(out.get(k)) for k in self.RAY_WANT], eng.stream), 'ra_mesh_raycast')
         return out
 
+    def icp_residual(self, points, point_normals, face_normals, dist_th=0.1, angle_th=0.7071067811865476, want_grad=True, want_keep=False):
+        """points, point_normals (n,3), face_normals (F,3) of THIS mesh in its original face order -> dotdict on the device
+        (ra_icp_residual): sums (2,) float64 — the sum of |p - closest|^2 over the kept rows and their count; loss = sums[0] /
+        sums[1], a float64 scalar (NaN when nothing is kept); grad (n,3) float32 = d loss / d points with the closest points held
+        constant; keep (n,) bool.  Kept: squared distance < fl32(dist_th^2) and dot(face_normals[face], point_normals) > angle_th."""
+        eng = self._live_engine()
+        d = eng.device
+        p, n0, n1 = _f32(points.reshape(-1, 3), d), _f32(point_normals.reshape(-1, 3), d), _f32(face_normals.reshape(-1, 3), d)
+        n = p.shape[0]
+        if n0.shape != p.shape or n1.shape[0] != self.n_faces:
+            raise ValueError(f'Mesh.icp_residual: point_normals must be ({n}, 3) and face_normals ({self.n_faces}, 3)')
+        out = dotdict(sums=torch.empty(2, dtype=torch.float64, device=d))
+        if want_grad:
+            out.grad = torch.zeros(n, 3, dtype=torch.float32, device=d)
+        keep = torch.zeros(n, dtype=torch.uint8, device=d) if want_keep else None
+        check(eng.lib.ra_icp_residual(eng.ctx, self._handle, _ptr(p) if n else None, _ptr(n0) if n else None, n, _ptr(n1) if n else None, float(dist_th),
+                                      float(angle_th), _ptr(out.sums), _ptr(out.grad) if want_grad and n else None, _ptr(keep) if want_keep and n else None,
+                                      eng.stream), 'ra_icp_residual')
+        out.loss = out.sums[0] / out.sums[1]
+        if want_keep:
+            out.keep = keep != 0
+        return out
+
     def close(self):
         eng = self._engine()
         if self._handle.value and eng is not None and eng.ctx.value:
@@ -268,6 +291,65 @@ class Topology:
         check(eng.lib.ra_topo_dilate(eng.ctx, self._handle, _ptr(src), self.V, abs(steps), _ptr(out), eng.stream), 'ra_topo_dilate')
         out = out != 0
         return ~out if steps < 0 else out
+
+    def _rows(self, who, x, eng):
+        v = _f32(x, eng.device)
+        if v.shape[:1] != (self.V,) or v.ndim not in (1, 2) or (v.ndim == 2 and not 1 <= v.shape[1] <= 64):
+            raise ValueError(f'Topology.{who}: rows must be ({self.V}, C) with 1 <= C <= 64, or ({self.V},)')
+        return v, v.reshape(self.V, 1 if v.ndim == 1 else v.shape[1])
+
+    def diffuse_apply(self, x, lam):
+        """x (V,C) or (V,) -> M x as a new float32 tensor, M = I + lam L the large-steps operator on this topology's unique edges
+        (ra_topo_diffuse_apply): largesteps' to_differential."""
+        eng = self._live_engine()
+        v, v2 = self._rows('diffuse_apply', x, eng)
+        out = torch.empty_like(v2)
+        check(eng.lib.ra_topo_diffuse_apply(eng.ctx, self._handle, _ptr(v2) if self.V else None, self.V, max(v2.shape[1], 1), float(lam),
+                                            _ptr(out) if self.V else None, eng.stream), 'ra_topo_diffuse_apply')
+        return out.reshape(v.shape)
+
+    def diffuse_solve(self, b, lam, x0=None, tol=1e-9, max_iter=256, info=False):
+        """b (V,C) or (V,) -> x with M x = b as a new float32 tensor (ra_topo_diffuse_solve): Jacobi-preconditioned conjugate
+        gradients in float64, every channel its own system, stopped at |r| <= tol |b| or after max_iter iterations; x0 warm-starts
+        it.  Nothing is read back.  info=True: (x, dotdict(iters (C,) int32, stop (C,) int32, residual (C,) float64)) on the device."""
+        eng = self._live_engine()
+        v, v2 = self._rows('diffuse_solve', b, eng)
+        start = None
+        if x0 is not None:
+            start = _f32(x0, eng.device).reshape(self.V, -1)
+            if start.shape != v2.shape:
+                raise ValueError('Topology.diffuse_solve: x0 must have the shape of b')
+        out = torch.empty_like(v2)
+        Cn = max(v2.shape[1], 1)
+        rec = torch.zeros(Cn, 2, dtype=torch.float64, device=eng.device) if info else None
+        check(eng.lib.ra_topo_diffuse_solve(eng.ctx, self._handle, _ptr(v2) if self.V else None, self.V, Cn, float(lam),
+                                            _ptr(start) if start is not None and self.V else None, float(tol), int(max_iter),
+                                            _ptr(out) if self.V else None, _ptr(rec), eng.stream), 'ra_topo_diffuse_solve')
+        out = out.reshape(v.shape)
+        if not info:
+            return out
+        words = rec[:, 0].contiguous().view(torch.int32).view(Cn, 2)
+        return out, dotdict(iters=words[:, 0], stop=words[:, 1], residual=rec[:, 1])
+
+    NORMALS = ('face_normal', 'face_area', 'vert_normal')
+
+    def normals(self, verts, want=NORMALS):
+        """verts (V,3) -> dotdict of the wanted float32 outputs on the device (ra_mesh_normals): face_normal (F,3) the reference's
+        face_normals, face_area (F,) its get_face_areas, vert_normal (V,3) the area-weighted vertex normals of pytorch3d."""
+        eng = self._live_engine()
+        want = tuple(want)
+        if not want or any(k not in self.NORMALS for k in want):
+            raise ValueError(f'Topology.normals: want must be a non-empty subset of {self.NORMALS}')
+        v = _f32(verts, eng.device)
+        if v.shape != (self.V, 3):
+            raise ValueError(f'Topology.normals: verts must be ({self.V}, 3)')
+        out = dotdict()
+        for k in want:
+            out[k] = torch.zeros({'face_normal': (self.F, 3), 'face_area': (self.F,), 'vert_normal': (self.V, 3)}[k], dtype=torch.float32, device=eng.device)
+        ptrs = [_ptr(out[k]) if k in out and out[k].numel() else None for k in self.NORMALS]
+        if any(p is not None for p in ptrs):      # an empty output has no address
+            check(eng.lib.ra_mesh_normals(eng.ctx, self._handle, _ptr(v), self.V, *ptrs, eng.stream), 'ra_mesh_normals')
+        return out
 
     def close(self):
         eng = self._engine()
@@ -795,6 +877,18 @@ class Engine:
         handle = C.c_void_p()
         check(self.lib.ra_topo_create(self.ctx, _ptr(f) if f.shape[0] else None, f.shape[0], int(n_verts), C.byref(handle), self.stream), 'ra_topo_create')
         return Topology(self, handle)
+
+    def adam_uniform_step(self, param, grad, g1, g2, step, lr=0.1, betas=(0.9, 0.999)):
+        """one AdamUniform step IN PLACE on float32 device tensors (include/relightableavatar.h: ra_adam_uniform_step): param, grad and
+        g1 of one shape, g2 a single float; step = 1, 2, ..."""
+        for name, t in (('param', param), ('grad', grad), ('g1', g1), ('g2', g2)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f'Engine.adam_uniform_step: {name} must be a contiguous float32 tensor on the device')
+        if grad.shape != param.shape or g1.shape != param.shape or g2.numel() != 1:
+            raise ValueError('Engine.adam_uniform_step: grad and g1 must have the shape of param, g2 one element')
+        n = param.numel()
+        check(self.lib.ra_adam_uniform_step(self.ctx, _ptr(param) if n else None, _ptr(grad) if n else None, _ptr(g1) if n else None, _ptr(g2), n, int(step),
+                                            float(lr), float(betas[0]), float(betas[1]), self.stream), 'ra_adam_uniform_step')
 
     def ray_tri_pairs(self, ray_o, ray_d, tris):
         """ray_o, ray_d (n,3), tris (F,3,3) -> (u, v, t), each (n,F) fp32 on the device: the reference's moller_trumbore for every

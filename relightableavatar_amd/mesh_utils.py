@@ -22,6 +22,9 @@
     halfedge_loop_subdivision / multiple_... / halfedge_to_triangle   :382-537 (Topology.subdivide: ra_mesh_subdivide)
     loop_subdivision(v, f, steps)                                     :204-207
     get_face_connectivity(faces)                                      :146-168
+    face_normals(v, f) / get_face_areas(v, f) / get_edge_length(v, e) :130-143, 193-201, 171-174 (Topology.normals: ra_mesh_normals)
+    icp_loss(v, t, n0, n1, dist_th, angle_th)                         :265-291 (Mesh.icp_residual: ra_icp_residual)
+    bidirectional_icp_fitting(v0, f0, v1, f1, ...)                    :294-379 (relightableavatar_amd.largesteps)
 
 The distance and winding functions take the engine that owns the HIP context (engine=, default: evaluators.mesh_evaluator.Evaluator.engine); they
 have no CPU fallback.  sample_blend_K_closest_points, sample_closest_points, the grid helpers, sample_surface and load_obj are plain torch / text and run anywhere.  Batches: the reference's signatures carry a
@@ -456,3 +459,112 @@ def loop_subdivision(v: torch.Tensor, f: torch.Tensor, steps=2, engine=None):
     """lib/utils/mesh_utils.py:204-207: `steps` Loop subdivision steps -> (verts float32, faces int64) on the device.  One
     blocking read-back in all (the first topology's); the later levels come from index arithmetic."""
     return halfedge_to_triangle(multiple_halfedge_loop_subdivision(triangle_to_halfedge(v, f, engine=engine), steps))
+
+
+# ---------------------------------------------------------------------- fitting one mesh to another (ra_fit.hip; .largesteps)
+def face_normals(v: torch.Tensor, f: torch.Tensor, engine=None) -> torch.Tensor:
+    """lib/utils/mesh_utils.py:130-143: v (V,3), f (F,3) -> (F,3) float32 on the device, normalize((v1 - v0) x (v2 - v1)) with the
+    reference's eps (Topology.normals: ra_mesh_normals).  No batch dimension."""
+    if v.ndim != 2 or v.shape[-1] != 3:
+        raise ValueError('face_normals: v (V,3), f (F,3); batches are not supported')
+    return _topology(f, v.shape[0], engine).normals(v, want=('face_normal',)).face_normal
+
+
+def get_face_areas(v: torch.Tensor, f: torch.Tensor, engine=None) -> torch.Tensor:
+    """lib/utils/mesh_utils.py:193-201: (F,) float32 on the device, |(v2 - v0) x (v1 - v0)| / 2"""
+    if v.ndim != 2 or v.shape[-1] != 3:
+        raise ValueError('get_face_areas: v (V,3), f (F,3); batches are not supported')
+    return _topology(f, v.shape[0], engine).normals(v, want=('face_area',)).face_area
+
+
+def get_edge_length(v: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """lib/utils/mesh_utils.py:171-174: v (..., V, 3), e (E,2) -> (..., E) the length of every edge; a gather and a norm in plain torch"""
+    e = e.to(v.device).long()
+    return torch.norm(v[..., e[:, 0], :] - v[..., e[:, 1], :], dim=-1)
+
+
+class _IcpLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v, mesh, n0, n1, dist_th, angle_th):
+        out = mesh.icp_residual(v, n0, n1, dist_th, angle_th, want_grad=True)
+        ctx.save_for_backward(out.grad)
+        ctx.shape, ctx.dtype = v.shape, v.dtype
+        return out.loss.to(v.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return (g.to(grad.dtype) * grad).reshape(ctx.shape).to(ctx.dtype), None, None, None, None, None
+
+
+def icp_loss(v: torch.Tensor, t, n0: torch.Tensor, n1: torch.Tensor, dist_th: float = 0.1, angle_th: float = float(np.cos(np.deg2rad(45.0))), engine=None):
+    """lib/utils/mesh_utils.py:265-291: the mean squared distance of the points v (N,3) with normals n0 to their closest points on
+    the target, over the rows that are nearer than dist_th and whose normal is within angle_th (a cosine) of the closest face's, n1
+    (F,3).  t: the target as an engine Mesh, or its triangles (F,3,3) as in the reference (a Mesh is then built for this call).
+    Differentiable in v only, with the closest points held constant — bvh_distance_queries returns them without gradient, so the
+    reference's gradient is this one: plain ICP.  Nothing is kept: NaN, gradient 0 (the reference's empty mean)."""
+    if v.ndim != 2 or v.shape[-1] != 3:
+        raise ValueError('icp_loss: v (N,3); batches are not supported')
+    own = torch.is_tensor(t)
+    if own:
+        if t.ndim != 3 or t.shape[1:] != (3, 3):
+            raise ValueError('icp_loss: t must be an engine Mesh or triangles (F,3,3)')
+        t = _engine(engine).mesh(t.detach().reshape(-1, 3), torch.arange(t.shape[0] * 3, dtype=torch.int32).view(-1, 3))
+    try:
+        return _IcpLoss.apply(v, t, n0.detach(), n1.detach(), float(dist_th), float(angle_th))
+    finally:
+        if own:
+            t.close()
+
+
+def boundary_vertices(topo, dilate: int = 0) -> torch.Tensor:
+    """(V,) bool on the device: the ends of every edge that does not have exactly two half-edges, dilated `dilate` times through the
+    adjacency as the reference dilates them (:318-334: after a step a vertex is set when one of its neighbours was)"""
+    vm = torch.zeros(topo.V, dtype=torch.bool, device=topo.edges.device)
+    vm[topo.edges[topo.edge_counts != 2].reshape(-1)] = True
+    return topo.dilate(vm, abs(int(dilate))) if dilate else vm
+
+
+def bidirectional_icp_fitting(v0: torch.Tensor, f0: torch.Tensor, v1: torch.Tensor, f1: torch.Tensor, lambda_smooth: int = 29, opt_iter: int = 500,
+                              ep_iter: int = 50, lr: float = 3e-2, boundary_focus: bool = True, dilate: int = 0, engine=None, verbose=True):
+    """lib/utils/mesh_utils.py:294-379: move two meshes onto each other.  Both are parameterised by u = (I + lambda L) v
+    (relightableavatar_amd.largesteps) and optimised with AdamUniform on icp_loss(v0 -> mesh 1) + icp_loss(v1 -> mesh 0); with
+    boundary_focus only the boundary vertices (dilated `dilate` times) enter the losses.  Returns the two float32 vertex arrays on
+    the device.  Per iteration the two solves are warm-started from the previous vertices and the two target meshes are rebuilt from
+    the moved vertices; nothing is read back except the loss every ep_iter iterations (verbose).  The target's face normals are the
+    reference's face_normals where the reference asks pytorch3d (the same direction; they only enter the angle filter).  A mesh
+    without boundary vertices under boundary_focus raises ValueError: the reference would optimise the NaN of an empty mean."""
+    from . import largesteps
+    eng = _engine(engine)
+    dev = eng.device
+    verts = [v0.detach().to(dev, torch.float32).contiguous(), v1.detach().to(dev, torch.float32).contiguous()]
+    faces_host = [f.detach().to('cpu', torch.int32).reshape(-1, 3).contiguous() for f in (f0, f1)]
+    M = [largesteps.compute_matrix(verts[k], faces_host[k], lambda_smooth, engine=eng) for k in range(2)]
+    sel = [None, None]
+    if boundary_focus:
+        for k in range(2):
+            vm = boundary_vertices(M[k].topology, dilate)
+            sel[k] = vm.nonzero(as_tuple=True)[0]
+            if sel[k].numel() == 0:
+                raise ValueError(f'bidirectional_icp_fitting: boundary_focus needs boundary vertices, mesh {k} has none (a closed mesh): pass boundary_focus=False')
+    p = [largesteps.to_differential(M[k], verts[k]).detach().requires_grad_() for k in range(2)]
+    optim = largesteps.AdamUniform(p, lr=lr, engine=eng)
+    for i in range(int(opt_iter)):
+        w = [largesteps.from_differential(M[k], p[k], 'Cholesky', x0=verts[k]) for k in range(2)]
+        verts = [x.detach() for x in w]
+        nrm = [M[k].topology.normals(verts[k], want=('face_normal', 'vert_normal')) for k in range(2)]
+        meshes = [eng.mesh(verts[k], faces_host[k]) for k in range(2)]
+        try:
+            loss = 0
+            for k in range(2):
+                pts, nv = (w[k], nrm[k].vert_normal) if sel[k] is None else (w[k][sel[k]], nrm[k].vert_normal[sel[k]])
+                loss = loss + icp_loss(pts, meshes[1 - k], nv, nrm[1 - k].face_normal)
+            optim.zero_grad(set_to_none=True)
+            loss.backward()
+            optim.step()
+        finally:
+            for m in meshes:
+                m.close()
+        if verbose and i % int(ep_iter) == 0:
+            print(f'bidirectional L2 loss: {loss.item():.5g}')
+    return tuple(M[k].solve(p[k].detach(), x0=verts[k]) for k in range(2))
