@@ -855,6 +855,55 @@ int ra_adam_uniform_step(ra_ctx* ctx, float* param_dev, const float* grad_dev, f
 /* test hook: 0 vertices of one channel per workgroup of the solve's kernels, 1 rows per workgroup of the residual's */
 int ra_fit_tile(int which);
 
+/* ---- cloth energies: the garment model of lib/utils/physx_utils.py (StVKMaterial, Garment, stretch_energy :242-267, bending_energy
+ * :270-311, gravity_energy, inertia_term / dynamic_term :322-351) with the gradient with respect to the vertex positions ----
+ * An ra_cloth is an immutable garment on a topology: per face the rest area (get_face_areas) and Dm_inv — get_shape_matrix of the 2-D
+ * material triangle vm[fm], inverted as torch_inverse_2x2 does, its det + 2^-23 included —, per vertex the mass
+ * (the sum of density area / 3 over its faces in ascending outgoing-half-edge order; a vertex no face uses has mass 0 and
+ * inv_mass = inf) and, per EDGE of the topology, a hinge where the edge has exactly two half-edges.  Hinges are addressed by edge id:
+ * in edge order they are the reference's get_face_connectivity, the lower half-edge's face first.  It belongs to its ctx (freed by
+ * ra_cloth_destroy or with the ctx) and reads its topology, which must outlive it (ra_topo_destroy refuses meanwhile).
+ * rest_verts_dev: n_verts x 3 fp32; vm_dev: n_vm x 2 fp32; fm_dev: n_faces x 3 int32, checked on the device against [0, n_vm) before
+ * anything dereferences it — the ONE blocking read-back of the build (4 bytes).  The material's derived coefficients (A,
+ * stretch_coeff, bending_coeff, lame_mu, lame_lambda: ra_cloth_material_derive, HOST, float64, StVKMaterial.__init__) are computed in
+ * float64 and rounded once.  Arrays (ra_cloth_array, DEVICE, asynchronous): F_AREA F fp32, DM and DM_INV F x 4 fp32 (row-major 2 x 2),
+ * V_MASS and INV_MASS V fp32, HINGE_FACES and HINGE_VERTS E x 2 int32 with -1 where the edge is no hinge.
+ * Errors: "null argument", "bad sizes" (n_verts of the topology, n_vm, 18 E < 2^31), "bad material" (a non-finite parameter),
+ * "material index" (fm outside [0, n_vm)), "not a topology / cloth of this ctx", "unknown array". */
+typedef struct ra_cloth ra_cloth;
+typedef struct ra_cloth_material {
+    double density, thickness, young_modulus, poisson_ratio, bending_multiplier, stretch_multiplier, material_multiplier;
+} ra_cloth_material;
+enum { RA_CLOTH_F_AREA = 0, RA_CLOTH_DM = 1, RA_CLOTH_DM_INV = 2, RA_CLOTH_V_MASS = 3, RA_CLOTH_INV_MASS = 4, RA_CLOTH_HINGE_FACES = 5,
+       RA_CLOTH_HINGE_VERTS = 6 };
+enum { RA_CLOTH_STRETCH = 1, RA_CLOTH_BENDING = 2, RA_CLOTH_GRAVITY = 4 };
+int ra_cloth_material_derive(const ra_cloth_material* material, double* out5);
+int ra_cloth_create(ra_ctx* ctx, const ra_topo* topo, const float* rest_verts_dev, int n_verts, const float* vm_dev, int n_vm, const int* fm_dev,
+                    const ra_cloth_material* material, ra_cloth** cloth, void* stream);
+int ra_cloth_destroy(ra_ctx* ctx, ra_cloth* cloth);
+int ra_cloth_array(ra_ctx* ctx, const ra_cloth* cloth, int which, void* out_dev, void* stream);
+/* The selected terms (a bit set of RA_CLOTH_STRETCH, _BENDING, _GRAVITY) at B rows of positions x_dev (B x n_verts x 3 fp32).
+ *   energy_dev  DEVICE float64 B x 3: per row the sums of the per-face stretch, per-hinge bending and per-vertex gravity (g mass y)
+ *               energies, 0 for a term that is not selected; NOT divided by B
+ *   grad_dev    (nullable) B x n_verts x 3 fp32: the gradient of the row's selected terms' sum with respect to x
+ * Element arithmetic is fp32, one named operation per rounding (csrc/ra_cloth_rules.hpp).  Element kernels write corner gradients to
+ * scratch; a vertex kernel adds a vertex's face corners in ascending half-edge order, then its hinge slots in ascending (hinge, slot)
+ * order, each term on its own, and then (stretch + bending) + gravity.  Energies are float64 sums in fixed chunks of one row.  No float
+ * atomics: row b of every output is a function of x[b] and the cloth alone, bit for bit — not of B, the other rows, the other
+ * selected terms or the launch geometry.  Asynchronous, no read-back.
+ * Errors: "null argument", "bad sizes" (1 <= B <= 65535, B x elements < 2^31), "bad terms" (none, or an unknown bit), "bad gravity"
+ * (NaN), "not a cloth of this ctx". */
+int ra_cloth_energy(ra_ctx* ctx, const ra_cloth* cloth, const float* x_dev, int B, int terms, float gravity, double* energy_dev, float* grad_dev,
+                    void* stream);
+/* inertia_term, or dynamic_term when accel3 (HOST, 3 floats) is non-NULL, over rows x V vertices with mass_dev (V fp32):
+ * d = x_next - (x_curr + dt v_curr (+ dt dt accel)), value_dev[row] (DEVICE float64) = the row's sum of (d . d) mass / (2 dt dt), NOT
+ * divided by rows; g_next = d mass / (dt dt), g_curr = -g_next, g_vel = -dt g_next (each nullable, rows x V x 3 fp32).
+ * Errors: "null argument", "bad sizes" (1 <= rows <= 65535, V >= 1, rows x V < 2^31), "bad delta_t" (NaN or 0). */
+int ra_cloth_inertia(ra_ctx* ctx, const float* mass_dev, const float* x_next_dev, const float* x_curr_dev, const float* v_curr_dev, int rows, int V,
+                     float delta_t, const float* accel3, double* value_dev, float* g_next_dev, float* g_curr_dev, float* g_vel_dev, void* stream);
+/* test hook: elements per workgroup of 0 the face kernel, 1 the hinge kernel, 2 the vertex kernel; 3 elements per chunk of an energy sum */
+int ra_cloth_tile(int which);
+
 /* ---- mesh extraction: the two steps the reference's mesh renderer leaves to mcubes and trimesh (mesh_renderer.py:74-84) ----
  * ra_marching_cubes: classic marching cubes on a DEVICE volume of nx x ny x nz fp32 values, x slowest (what reshape gives), with the
  * classic corner and edge numbering, 256-entry tables derived by rule (relightableavatar_amd/mcubes_tables.py) and linear

@@ -16,6 +16,10 @@ RA_WINDING_ONE_PASS, RA_WINDING_SPLIT = 1, 2      # flags of ra_mesh_winding
 RA_RAYCAST_BRUTE, RA_RAYCAST_UNSORTED = 1, 2      # flags of ra_mesh_raycast
 # the arrays of ra_topo_array, in the header's order
 RA_TOPO_ARRAYS = ('vert', 'twin', 'edge', 'edges', 'edge_counts', 'edge_he_start', 'edge_he', 'nbr_start', 'nbr', 'out_start', 'out_he')
+RA_CLOTH_STRETCH, RA_CLOTH_BENDING, RA_CLOTH_GRAVITY = 1, 2, 4      # terms of ra_cloth_energy
+# the fields of ra_cloth_material in the header's order, with the reference's StVKMaterial defaults
+CLOTH_MATERIAL_DEFAULTS = (('density', 426 * 0.00047), ('thickness', 0.00047), ('young_modulus', 0.7e5), ('poisson_ratio', 0.485),
+                           ('bending_multiplier', 50.0), ('stretch_multiplier', 1.0), ('material_multiplier', 1.0))
 RA_VOLUME_MODES = {'canonical': 0, 'tpose': 1, 'posed': 2}      # modes of ra_sdf_volume
 
 
@@ -98,6 +102,10 @@ class ra_metrics_params(C.Structure):
 
 class ra_lpips_weights(C.Structure):
     _fields_ = [('conv_w', C.c_void_p * 5), ('conv_b', C.c_void_p * 5), ('lin', C.c_void_p * 5), ('shift', C.c_float * 3), ('scale', C.c_float * 3)]
+
+
+class ra_cloth_material(C.Structure):
+    _fields_ = [(k, C.c_double) for k, _ in CLOTH_MATERIAL_DEFAULTS]
 
 
 class ra_counters(C.Structure):
@@ -192,6 +200,14 @@ SYMBOLS = {
     'ra_icp_residual': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 4),
     'ra_adam_uniform_step': (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     'ra_fit_tile': (C.c_int, [C.c_int]),
+    'ra_cloth_material_derive': (C.c_int, [C.POINTER(ra_cloth_material), C.POINTER(C.c_double)]),
+    'ra_cloth_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(ra_cloth_material),
+                                  C.POINTER(C.c_void_p), C.c_void_p]),
+    'ra_cloth_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'ra_cloth_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_cloth_energy': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ra_cloth_inertia': (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float)] + [C.c_void_p] * 5),
+    'ra_cloth_tile': (C.c_int, [C.c_int]),
     'ra_ray_tri_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     'ra_sdf_volume': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                 C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

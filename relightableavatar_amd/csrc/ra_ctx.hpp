@@ -87,6 +87,15 @@ struct ra_topo {
     std::vector<float> loop_w_host;
 };
 
+// A garment on a topology (ra_cloth_create, ra_cloth.hip): owned by its context (ra_ctx::cloths), immutable once built.  It reads its
+// topology's arrays, so the topology must outlive it.
+struct ra_cloth {
+    const ra_topo* topo = nullptr;
+    double coeffs[5] = {};              // A, stretch_coeff, bending_coeff, lame_mu, lame_lambda (float64, host)
+    float thickness = 0.f, mu = 0.f, lambda = 0.f, bending = 0.f;       // rounded once
+    DevBuf frec, f_area, dm, dm_inv, hrec, h_faces, h_verts, mass, inv_mass, vh, vh_count;
+};
+
 // The size query of ra_marching_cubes / ra_mesh_largest_component that the next writing call completes: what it was asked and what it
 // answered.  The offsets it computed stay in the context's scratch ("mc_*", "lcc_*") until then.
 struct McQuery {
@@ -138,6 +147,8 @@ struct ra_ctx {
     std::vector<std::unique_ptr<ra_mesh>> meshes;
     // mesh connectivity still alive (ra_topo_create); freed with the context
     std::vector<std::unique_ptr<ra_topo>> topos;
+    // garments still alive (ra_cloth_create); freed with the context
+    std::vector<std::unique_ptr<ra_cloth>> cloths;
     // mesh extraction: the pending size queries (ra_marching_cubes, ra_mesh_largest_component)
     int vol_readbacks = 0;      // blocking read-backs of the last ra_sdf_volume
     McQuery mc_query;

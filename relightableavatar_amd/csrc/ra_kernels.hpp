@@ -374,6 +374,44 @@ void launch_icp_residual(const IcpJob& j, double* sums, float* grad, hipStream_t
 void launch_adam_uniform(float* param, const float* grad, float* g1, float* g2, long long n, unsigned* scratch, double lr, double b1, double b2, double c1,
                          double c2, hipStream_t s);
 
+// Cloth energies (ra_cloth.hip): StVK stretch per face, dihedral bending per hinge (addressed by edge id), gravity, inertia
+constexpr int CLOTH_BLOCK = 256;                 // (row, face) / (row, edge) / (row, vertex) elements per workgroup
+constexpr int CLOTH_CHUNK = 2048;                // consecutive elements of one row per workgroup of an energy sum
+struct ClothBuild {
+    const float *rest, *vm;         // V x 3 rest positions, n_vm x 2 material coordinates
+    const int* fm;                  // F x 3 into vm, checked
+    float density;
+    float *frec, *f_area, *dm, *dm_inv;     // F x 8 records, F, F x 4, F x 4
+    int *hrec, *h_faces, *h_verts;          // E x 8 records, E x 2, E x 2 (-1: no hinge)
+    float *mass, *inv_mass;                 // V
+    int *vh, *vh_count;                     // 9 F (the segment of vertex v starts at 3 out_start[v]), V
+};
+struct ClothJob {
+    const float* x;                 // B x V x 3
+    int B, n_faces, n_edges, n_verts, terms;
+    float thickness, mu, lambda, bending, gravity;
+    const float* frec;
+    const int* hrec;
+    const float* mass;
+    const int *vh, *vh_count;
+    float *e_face, *e_hinge, *e_vert;       // B x F, B x E, B x V element energies
+    float *g_face, *g_hinge;                // B x F x 9, B x E x 18 corner gradients (only with grad)
+    double* part;                           // B x chunks of the largest element count
+    float* grad;                            // nullable: B x V x 3
+};
+struct InertiaJob {
+    const float *mass, *x_next, *x_curr, *v_curr;
+    int rows, V, has_accel;
+    float dt, accel[3];
+    float* el;                      // rows x V
+    double* part;
+    float *g_next, *g_curr, *g_vel; // nullable
+};
+void launch_cloth_check_fm(const int* fm, int n_faces, int n_vm, int* bad, hipStream_t s);
+void launch_cloth_build(const TopoView& t, const ClothBuild& b, hipStream_t s);
+void launch_cloth_energy(const TopoView& t, const ClothJob& j, double* energy, hipStream_t s);
+void launch_cloth_inertia(const InertiaJob& j, double* value, hipStream_t s);
+
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot
 void launch_scatter_maps(const int* hit_idx, const int* hit_count, int P, int premultiply, const float* acc_full,

@@ -364,6 +364,75 @@ class Topology:
             pass
 
 
+class Cloth:
+    """a garment on a Topology (Engine.cloth; include/relightableavatar.h: ra_cloth_create): rest areas, Dm_inv, vertex masses and the
+    hinges of the manifold edges, immutable, on the device.  It keeps its Topology alive.  close() — or garbage collection — releases
+    it while the engine lives."""
+
+    TERMS = {'stretch': _lib.RA_CLOTH_STRETCH, 'bending': _lib.RA_CLOTH_BENDING, 'gravity': _lib.RA_CLOTH_GRAVITY}
+
+    def __init__(self, engine, handle, topology, coeffs):
+        self._engine, self._handle, self.topology, self._cache = weakref.ref(engine), handle, topology, None
+        self.coeffs = coeffs        # A, stretch_coeff, bending_coeff, lame_mu, lame_lambda as the library derived them (float64)
+
+    def _live_engine(self):
+        eng = self._engine()
+        if eng is None or not eng.ctx.value:
+            raise _lib.RaError('Cloth: the engine that built this cloth is gone')
+        if not self._handle.value:
+            raise _lib.RaError('Cloth: closed')
+        return eng
+
+    @property
+    def arrays(self):
+        """dotdict on the device: f_area (F,), Dm and Dm_inv (F,2,2), v_mass and inv_mass (V,) float32; f_connectivity and
+        f_connectivity_edges (H,2) int64, the hinges in the order of Topology.face_connectivity().  The library keeps hinges per
+        edge; dropping the edges without one is a masked copy here (it waits for the device once), then cached."""
+        if self._cache is None:
+            eng, t = self._live_engine(), self.topology
+            out = dotdict()
+            for k, (name, n, dt) in enumerate((('f_area', t.F, torch.float32), ('Dm', 4 * t.F, torch.float32), ('Dm_inv', 4 * t.F, torch.float32),
+                                               ('v_mass', t.V, torch.float32), ('inv_mass', t.V, torch.float32), ('hinge_faces', 2 * t.E, torch.int32),
+                                               ('hinge_verts', 2 * t.E, torch.int32))):
+                a = torch.empty(n, dtype=dt, device=eng.device)
+                check(eng.lib.ra_cloth_array(eng.ctx, self._handle, k, _ptr(a) if n else None, eng.stream), 'ra_cloth_array')
+                out[name] = a
+            out.Dm, out.Dm_inv = out.Dm.view(-1, 2, 2), out.Dm_inv.view(-1, 2, 2)
+            hf, hv = out.pop('hinge_faces').view(-1, 2).long(), out.pop('hinge_verts').view(-1, 2).long()
+            keep = hf[:, 0] >= 0
+            out.f_connectivity, out.f_connectivity_edges = hf[keep], hv[keep]
+            self._cache = out
+        return self._cache
+
+    def energy(self, x, terms=('stretch', 'bending'), gravity=9.81, grad=True):
+        """x (B,V,3) -> (energy (B,3) float64: the per-row stretch, bending and gravity sums, 0 where a term is not selected; grad
+        (B,V,3) float32 of the selected terms' sum, or None) on the device (ra_cloth_energy).  Not divided by B.  Asynchronous."""
+        eng = self._live_engine()
+        v = _f32(x, eng.device)
+        if v.ndim != 3 or v.shape[1:] != (self.topology.V, 3) or v.shape[0] < 1:
+            raise ValueError(f'Cloth.energy: x must be (B, {self.topology.V}, 3) with B >= 1')
+        bits = 0
+        for k in terms:
+            bits |= self.TERMS[k]
+        energy = torch.empty(v.shape[0], 3, dtype=torch.float64, device=eng.device)
+        g = torch.empty_like(v) if grad else None
+        check(eng.lib.ra_cloth_energy(eng.ctx, self._handle, _ptr(v) if v.numel() else None, v.shape[0], bits, float(gravity), _ptr(energy),
+                                      _ptr(g) if g is not None and g.numel() else None, eng.stream), 'ra_cloth_energy')
+        return energy, g
+
+    def close(self):
+        eng = self._engine()
+        if self._handle.value and eng is not None and eng.ctx.value:
+            check(eng.lib.ra_cloth_destroy(eng.ctx, self._handle), 'ra_cloth_destroy')
+        self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     def __init__(self, cfg, device=None, relight=False):
         if not torch.cuda.is_available():
@@ -877,6 +946,39 @@ class Engine:
         handle = C.c_void_p()
         check(self.lib.ra_topo_create(self.ctx, _ptr(f) if f.shape[0] else None, f.shape[0], int(n_verts), C.byref(handle), self.stream), 'ra_topo_create')
         return Topology(self, handle)
+
+    def cloth(self, topology, rest_verts, vm, fm, material=None):
+        """topology (Engine.topology), rest_verts (V,3), vm (M,2) material coordinates, fm (F,3) integers into vm, material (an
+        object or dict with density, thickness, young_modulus, poisson_ratio, bending_multiplier, stretch_multiplier and optionally
+        material_multiplier; None: the reference's StVKMaterial defaults) -> a Cloth handle (include/relightableavatar.h:
+        ra_cloth_create).  One 4-byte read-back: the verdict on fm."""
+        get = (lambda k, d: material.get(k, d)) if isinstance(material, dict) else (lambda k, d: getattr(material, k, d))
+        m = _lib.ra_cloth_material(*[float(get(k, d)) for k, d in _lib.CLOTH_MATERIAL_DEFAULTS])
+        v = _f32(rest_verts.reshape(-1, 3), self.device)
+        vm = _f32(vm.reshape(-1, 2), self.device)
+        fm = fm.detach().to(device=self.device, dtype=torch.int32).reshape(-1, 3).contiguous()
+        if fm.shape[0] != topology.F:
+            raise ValueError(f'Engine.cloth: fm must be ({topology.F}, 3)')
+        handle = C.c_void_p()
+        check(self.lib.ra_cloth_create(self.ctx, topology._handle, _ptr(v) if v.numel() else None, v.shape[0], _ptr(vm) if vm.numel() else None,
+                                       vm.shape[0], _ptr(fm) if fm.numel() else None, C.byref(m), C.byref(handle), self.stream), 'ra_cloth_create')
+        coeffs = (C.c_double * 5)()
+        check(self.lib.ra_cloth_material_derive(C.byref(m), coeffs), 'ra_cloth_material_derive')
+        return Cloth(self, handle, topology, tuple(coeffs))
+
+    def cloth_inertia(self, mass, x_next, x_curr, v_curr, delta_t, accel=None, grads=(True, True, True)):
+        """mass (V,), x_next, x_curr, v_curr (rows,V,3) -> (value (rows,) float64 per-row sums, g_next, g_curr, g_vel (rows,V,3) float32
+        or None where not wanted) on the device (ra_cloth_inertia): inertia_term, or dynamic_term with accel (3 floats)"""
+        d = self.device
+        m, a, b, c = _f32(mass.reshape(-1), d), _f32(x_next, d), _f32(x_curr, d), _f32(v_curr, d)
+        if a.ndim != 3 or a.shape[1:] != (m.shape[0], 3) or b.shape != a.shape or c.shape != a.shape:
+            raise ValueError('cloth_inertia: x_next, x_curr, v_curr must be (rows, V, 3) with V the length of mass')
+        value = torch.empty(a.shape[0], dtype=torch.float64, device=d)
+        outs = [torch.empty_like(a) if w else None for w in grads]
+        acc = (C.c_float * 3)(*[float(t) for t in accel]) if accel is not None else None
+        check(self.lib.ra_cloth_inertia(self.ctx, _ptr(m), _ptr(a), _ptr(b), _ptr(c), a.shape[0], a.shape[1], float(delta_t), acc, _ptr(value),
+                                        *[_ptr(o) for o in outs], self.stream), 'ra_cloth_inertia')
+        return (value, *outs)
 
     def adam_uniform_step(self, param, grad, g1, g2, step, lr=0.1, betas=(0.9, 0.999)):
         """one AdamUniform step IN PLACE on float32 device tensors (include/relightableavatar.h: ra_adam_uniform_step): param, grad and

@@ -22,6 +22,7 @@
     halfedge_loop_subdivision / multiple_... / halfedge_to_triangle   :382-537 (Topology.subdivide: ra_mesh_subdivide)
     loop_subdivision(v, f, steps)                                     :204-207
     get_face_connectivity(faces)                                      :146-168
+    get_vertex_mass(v, f, density, areas=None)                        :177-190
     face_normals(v, f) / get_face_areas(v, f) / get_edge_length(v, e) :130-143, 193-201, 171-174 (Topology.normals: ra_mesh_normals)
     icp_loss(v, t, n0, n1, dist_th, angle_th)                         :265-291 (Mesh.icp_residual: ra_icp_residual)
     bidirectional_icp_fitting(v0, f0, v1, f1, ...)                    :294-379 (relightableavatar_amd.largesteps)
@@ -475,6 +476,22 @@ def get_face_areas(v: torch.Tensor, f: torch.Tensor, engine=None) -> torch.Tenso
     if v.ndim != 2 or v.shape[-1] != 3:
         raise ValueError('get_face_areas: v (V,3), f (F,3); batches are not supported')
     return _topology(f, v.shape[0], engine).normals(v, want=('face_area',)).face_area
+
+
+def get_vertex_mass(v: torch.Tensor, f: torch.Tensor, density: float, areas: torch.Tensor = None, engine=None) -> torch.Tensor:
+    """lib/utils/mesh_utils.py:177-190: v (V,3), f (F,3) -> (V,) float32 on the device, every vertex the sum of density area / 3 over
+    its faces in ascending outgoing-half-edge order (Engine.cloth: ra_cloth_create); a vertex no face uses weighs 0.  The SUM: the
+    reference's indexed `+=` keeps one face's share per corner slot.  With `areas` given the shares are those
+    areas' and the sum is torch's index_add_, whose order is not fixed."""
+    if v.ndim != 2 or v.shape[-1] != 3:
+        raise ValueError('get_vertex_mass: v (V,3), f (F,3); batches are not supported')
+    eng = _engine(engine)
+    if areas is not None:
+        share = (density * areas.to(eng.device, torch.float32) / 3)[:, None].expand(-1, 3).reshape(-1)
+        return torch.zeros(v.shape[0], dtype=torch.float32, device=eng.device).index_add_(0, f.to(eng.device).long().reshape(-1), share)
+    topo = _topology(f, v.shape[0], eng)
+    cloth = eng.cloth(topo, v, torch.zeros(1, 2), torch.zeros(f.shape[0], 3, dtype=torch.int32), dict(density=density))
+    return cloth.arrays.v_mass
 
 
 def get_edge_length(v: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
