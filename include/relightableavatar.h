@@ -691,6 +691,30 @@ enum { RA_WINDING_ONE_PASS = 1,   /* test and measurement hooks: every point sum
 int ra_mesh_winding(ra_ctx* ctx, const ra_mesh* mesh, const float* pts_dev, int n, int flags, float* winding_dev, void* stream);
 /* test hook: 0 points per tile (workgroup), 1 face records per chunk, 2 point tiles below which the faces are split across workgroups */
 int ra_winding_tile(int which);
+/* Per point (pts: DEVICE n x 3 fp32) the winding number of ra_mesh_winding AND its gradient with respect to the point: winding (n, may
+ * be NULL) and grad (n x 3), fp32.  What the reference gets from autograd through winding_number, in closed form: the gradient of the
+ * function ra_mesh_winding computes, its eps under the root included, not of the ideal solid angle.
+ * Per pair (ra_winding_grad_tri.hpp, every operation a named fp32 operation), with d_i = v_i - p:
+ *   grad (sign Omega) = k(T) sum over the edges (x, y) = (d0, d1), (d1, d2), (d2, d0) of (x cross y) (|x| + |y|) / (|x| |y| (|x| |y| + x.y)),
+ *   k(T) = (1 + T) sqrt(T) / ((1 + T + eps) sqrt(T + eps)),  T = tan^2(Omega_0 / 4),  eps = 1e-10
+ * — the Biot-Savart form of the gradient of the signed solid angle, times the derivative of 4 atan(sqrt(T + eps)) over that of
+ * 4 atan(sqrt(T)), which is far from 1 for a small or distant face.  The value is ra_mesh_winding's bit for bit: the pair's
+ * normalisations are formed once and serve both.  det == 0 (a point in a face's plane, a face of no area): value 0 and gradient 0.  A
+ * face dropped at ra_mesh_create contributes nothing.
+ * Sums: four float64 sums per point (value, gx, gy, gz), faces in the mesh's stored order in chunks of ra_winding_tile(1) records whose
+ * sums start from 0 and are added in chunk order; each is scaled by 1 / (4 pi) in float64 and rounded once to fp32.  A row is a
+ * function of (point, mesh) alone, bit for bit: not of n, of the order or the subset of the points, or of the launch shape (flags:
+ * RA_WINDING_ONE_PASS / RA_WINDING_SPLIT as for ra_mesh_winding; the default splits the faces across workgroups below
+ * ra_winding_tile(2) point tiles).
+ * Non-finite rows: a point with a non-finite coordinate and a point bit-equal to a vertex of a kept face (value and gradient NaN),
+ * and a point on the segment of an edge of a kept face — where the computed |x| |y| + x.y of that edge is not positive: the gradient
+ * is NaN (the solid angle jumps there), the value is ra_mesh_winding's.  No other row of the launch is affected.
+ * Asynchronous on stream, no read-back, no float atomics; n == 0 launches nothing and reads no pointer; scratch (the split launch's
+ * chunk sums, four float64 per point and chunk) is allocated on the first call of a size only and belongs to the ctx: the ordering
+ * rule of the other mesh calls holds.
+ * Errors: "null argument", "bad sizes" (n < 0, n >= 2^30), "unknown flag", "not a mesh of this ctx". */
+int ra_mesh_winding_grad(ra_ctx* ctx, const ra_mesh* mesh, const float* pts_dev, int n, int flags, float* winding_dev, float* grad_dev,
+                         void* stream);
 /* Per ray (ray_o, ray_d: DEVICE n x 3 fp32; d is not normalised, t is in units of |d|) where it meets the mesh: the reference's
  * moller_trumbore and ray_stabbing (lib/utils/mesh_utils.py:686-738) over the faces the mesh kept.
  *   t (n)       the smallest t over the faces the hit predicate accepts; +inf without a hit

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get('RA_LIB_PATH') or os.path.join(_HERE, 'librelightablea
 _lib = None
 ABI_VERSION = 9          # RA_ABI_VERSION of include/relightableavatar.h
 RA_MESH_BRUTE, RA_MESH_UNSORTED = 1, 2      # flags of ra_mesh_closest
-RA_WINDING_ONE_PASS, RA_WINDING_SPLIT = 1, 2      # flags of ra_mesh_winding
+RA_WINDING_ONE_PASS, RA_WINDING_SPLIT = 1, 2      # flags of ra_mesh_winding and ra_mesh_winding_grad
 RA_RAYCAST_BRUTE, RA_RAYCAST_UNSORTED = 1, 2      # flags of ra_mesh_raycast
 # the arrays of ra_topo_array, in the header's order
 RA_TOPO_ARRAYS = ('vert', 'twin', 'edge', 'edges', 'edge_counts', 'edge_he_start', 'edge_he', 'nbr_start', 'nbr', 'out_start', 'out_he')
@@ -182,6 +182,7 @@ SYMBOLS = {
     'ra_mesh_tile': (C.c_int, [C.c_int]),
     'ra_mesh_winding': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'ra_winding_tile': (C.c_int, [C.c_int]),
+    'ra_mesh_winding_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ra_mesh_raycast': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'ra_raycast_tile': (C.c_int, [C.c_int]),
     'ra_topo_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),

@@ -624,6 +624,29 @@ int ra_mesh_winding(ra_ctx* c, const ra_mesh* mesh, const float* pts, int n, int
     return 0;
 }
 
+int ra_mesh_winding_grad(ra_ctx* c, const ra_mesh* mesh, const float* pts, int n, int flags, float* winding, float* grad, void* stream) {
+    RA_CHECK(c && mesh, "ra_mesh_winding_grad: null argument");
+    RA_CHECK(find_mesh(c, mesh), "ra_mesh_winding_grad: not a mesh of this ctx");
+    RA_CHECK(n >= 0 && n < (1 << 30), "ra_mesh_winding_grad: bad sizes");
+    RA_CHECK((flags & ~(RA_WINDING_ONE_PASS | RA_WINDING_SPLIT)) == 0 && flags != (RA_WINDING_ONE_PASS | RA_WINDING_SPLIT), "ra_mesh_winding_grad: unknown flag");
+    if (n == 0) return 0;       // nothing to read or write: empty arrays have no address
+    RA_CHECK(pts && grad, "ra_mesh_winding_grad: null argument (pts, grad)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    // ra_mesh_winding's rule, with four float64 sums per (point, chunk) in the same budget of bytes
+    const long long n_chunks = wind_chunk_count(mesh->view.n_leaves), tiles = ((long long)n + WIND_BLOCK - 1) / WIND_BLOCK;
+    const bool split = (flags & RA_WINDING_SPLIT) || (!(flags & RA_WINDING_ONE_PASS) && n_chunks > 1 && tiles < WIND_SPLIT_TILES && n * n_chunks * 4 <= WIND_SPLIT_MAX);
+    double* partial = nullptr;
+    if (split) {
+        int err = 0;
+        partial = c->buf<double>("winding_grad_partial", (size_t)(n * n_chunks * 4), &err);
+        RA_CHECK(!err, "ra_mesh_winding_grad: out of device memory");
+    }
+    launch_mesh_winding_grad(mesh->view, pts, n, partial, winding, grad, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- ray-mesh intersection (ra_raycast.hip) -------------------------------------------------------
 int ra_raycast_tile(int which) { return which == 0 ? RAY_BLOCK : which == 1 ? RAY_PAIR_BLOCK : which == 2 ? MESH_SORT_MIN : 0; }
 

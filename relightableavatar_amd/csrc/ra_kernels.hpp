@@ -285,6 +285,9 @@ constexpr long long WIND_SPLIT_MAX = 1ll << 24;  // ... as long as points x chun
 inline int wind_chunk_count(int n_leaves) { return (int)(((long long)n_leaves * MESH_LEAF + WIND_CHUNK - 1) / WIND_CHUNK); }
 // partial: nullptr = the one-pass kernel; else chunks x n float64 of scratch = the split launch (the same bits)
 void launch_mesh_winding(const MeshView& m, const float* pts, int n, double* partial, float* out, hipStream_t s);
+// The same sweep with the gradient in the point (ra_winding_grad.hip): winding (nullable, n) and grad (n x 3); the same tiles and chunks.
+// partial: nullptr = the one-pass kernel; else chunks x 4 x n float64 of scratch = the split launch (the same bits)
+void launch_mesh_winding_grad(const MeshView& m, const float* pts, int n, double* partial, float* winding, float* grad, hipStream_t s);
 
 // Ray-mesh intersection over a mesh's box structure, and the dense ray x triangle pairs (ra_raycast.hip)
 constexpr int RAY_BLOCK = 64;                    // rays per workgroup: one wave

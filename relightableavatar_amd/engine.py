@@ -122,6 +122,22 @@ class Mesh:
         check(eng.lib.ra_mesh_winding(eng.ctx, self._handle, _ptr(pts), n, flags, _ptr(out), eng.stream), 'ra_mesh_winding')
         return out
 
+    def winding_grad(self, points, shape=None):
+        """points (n,3) -> (winding (n,), grad (n,3)) float32 on the device: Mesh.winding's number, the same bits, and its gradient with
+        respect to the point (include/relightableavatar.h: ra_mesh_winding_grad) — the gradient of the function Mesh.winding computes,
+        in closed form.  A row is a function of (point, mesh) alone, bit for bit.  A non-finite point and a point on a vertex: NaN in
+        both; a point on the segment of an edge: a NaN gradient.  shape: as Mesh.winding's.  Nothing is read back."""
+        eng = self._live_engine()
+        if shape not in (None, 'one_pass', 'split'):
+            raise ValueError("Mesh.winding_grad: shape must be None, 'one_pass' or 'split'")
+        pts = _f32(points.reshape(-1, 3), eng.device)
+        n = pts.shape[0]
+        w = torch.empty(n, dtype=torch.float32, device=eng.device)
+        grad = torch.empty((n, 3), dtype=torch.float32, device=eng.device)
+        flags = {None: 0, 'one_pass': _lib.RA_WINDING_ONE_PASS, 'split': _lib.RA_WINDING_SPLIT}[shape]
+        check(eng.lib.ra_mesh_winding_grad(eng.ctx, self._handle, _ptr(pts), n, flags, _ptr(w), _ptr(grad), eng.stream), 'ra_mesh_winding_grad')
+        return w, grad
+
     RAY_WANT = ('t', 'face', 'uv', 'count')
 
     def raycast(self, ray_o, ray_d, want=RAY_WANT, brute=False, sort=True):

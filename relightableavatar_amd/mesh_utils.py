@@ -26,10 +26,17 @@
     face_normals(v, f) / get_face_areas(v, f) / get_edge_length(v, e) :130-143, 193-201, 171-174 (Topology.normals: ra_mesh_normals)
     icp_loss(v, t, n0, n1, dist_th, angle_th)                         :265-291 (Mesh.icp_residual: ra_icp_residual)
     bidirectional_icp_fitting(v0, f0, v1, f1, ...)                    :294-379 (relightableavatar_amd.largesteps)
+    isosurface_fitting(src_verts, src_faces, tar_verts, tar_faces, ...)   :1018-1058 (Mesh.winding_grad: ra_mesh_winding_grad)
 
 The distance and winding functions take the engine that owns the HIP context (engine=, default: evaluators.mesh_evaluator.Evaluator.engine); they
 have no CPU fallback.  sample_blend_K_closest_points, sample_closest_points, the grid helpers, sample_surface and load_obj are plain torch / text and run anywhere.  Batches: the reference's signatures carry a
 batch dimension; B == 1 is supported, B > 1 is refused.
+
+Autograd.  winding_number, winding_number_nooom, bvh_distance and winding_distance are differentiable in pts, never in the mesh.  With
+pts.requires_grad the winding number comes from Mesh.winding_grad — the same bits, with the gradient of the computed function in
+closed form — and the distance's gradient is (p - closest) / d with the closest point held constant, which
+is also its true derivative (0 where d == 0).  Without it the calls made and the bits returned are those of the plain queries.
+mesh=: an engine Mesh already built of (verts, faces) serves the call and stays open; verts and faces are then not read.
 
 The remesh keeps the reference's sequence (grid, vertex filter, surface filter, winding, shift x distance, -10 fill, marching cubes,
 largest component, scale) with Engine.marching_cubes and Engine.largest_component in the places of mcubes and trimesh.  Not kept, as in
@@ -50,16 +57,65 @@ def _engine(engine):
     return engine
 
 
-def bvh_distance(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, engine=None) -> torch.Tensor:
+def _wants_grad(pts) -> bool:
+    return torch.is_grad_enabled() and pts.requires_grad
+
+
+class _MeshDistance(torch.autograd.Function):
+    """|p - closest|, with the closest point a constant of the backward"""
+
+    @staticmethod
+    def forward(ctx, pts, mesh):
+        out = mesh.closest(pts, want=('d2', 'closest'))
+        d = out.d2.sqrt()
+        diff = pts.detach().to(device=d.device, dtype=torch.float32).reshape(-1, 3) - out.closest
+        ctx.save_for_backward(torch.where((d > 0)[:, None], diff / d[:, None], torch.zeros_like(diff)))
+        ctx.like = (pts.shape, pts.device, pts.dtype)
+        return d
+
+    @staticmethod
+    def backward(ctx, g):
+        direction, = ctx.saved_tensors
+        return (g[:, None] * direction).reshape(ctx.like[0]).to(device=ctx.like[1], dtype=ctx.like[2]), None
+
+
+class _MeshWinding(torch.autograd.Function):
+    """Mesh.winding_grad: the value of Mesh.winding, and its gradient kept for the backward"""
+
+    @staticmethod
+    def forward(ctx, pts, mesh):
+        w, grad = mesh.winding_grad(pts)
+        ctx.save_for_backward(grad)
+        ctx.like = (pts.shape, pts.device, pts.dtype)
+        return w
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return (g[:, None] * grad).reshape(ctx.like[0]).to(device=ctx.like[1], dtype=ctx.like[2]), None
+
+
+def _mesh_distance(mesh, pts):
+    return _MeshDistance.apply(pts, mesh) if _wants_grad(pts) else mesh.closest(pts, want=('d2',)).d2.sqrt()
+
+
+def _mesh_winding(mesh, pts):
+    return _MeshWinding.apply(pts, mesh) if _wants_grad(pts) else mesh.winding(pts)
+
+
+def bvh_distance(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, engine=None, mesh=None) -> torch.Tensor:
     """pts (N,3), verts (V,3), faces (F,3) -> (N,) the plain (not squared) distance of every point to the mesh, |pts - closest| as the
-    reference computes it from bvh_distance_queries' closest points."""
-    if pts.ndim != 2 or verts.ndim != 2 or faces.ndim != 2:
+    reference computes it from bvh_distance_queries' closest points.  Differentiable in pts."""
+    if pts.ndim != 2 or (mesh is None and (verts.ndim != 2 or faces.ndim != 2)):
         raise ValueError('bvh_distance: pts (N,3), verts (V,3), faces (F,3) — the reference adds the batch dimension itself')
-    mesh = _engine(engine).mesh(verts, faces)
+    own = mesh is None
+    if own:
+        mesh = _engine(engine).mesh(verts, faces)
     try:
-        return mesh.closest(pts, want=('d2',)).d2.sqrt()
+        return _mesh_distance(mesh, pts)
     finally:
-        mesh.close()
+        if own:
+            mesh.close()
 
 
 def sample_closest_points_on_surface(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, values: torch.Tensor = None, engine=None):
@@ -212,15 +268,20 @@ def _check_mesh_args(what, pts, verts, faces):
         raise ValueError(f'{what}: pts (N,3), verts (V,3), faces (F,3); batches are not supported')
 
 
-def winding_number(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, engine=None) -> torch.Tensor:
+def winding_number(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, engine=None, mesh=None) -> torch.Tensor:
     """pts (N,3), verts (V,3), faces (F,3) -> (N,) float32 on the device: the generalised winding number of the mesh at every point,
-    Mesh.winding of a mesh built for this call."""
-    _check_mesh_args('winding_number', pts, verts, faces)
-    mesh = _engine(engine).mesh(verts, faces)
+    Mesh.winding of a mesh built for this call.  Differentiable in pts (Mesh.winding_grad)."""
+    own = mesh is None
+    if own:
+        _check_mesh_args('winding_number', pts, verts, faces)
+        mesh = _engine(engine).mesh(verts, faces)
+    elif pts.ndim != 2:
+        raise ValueError('winding_number: pts (N,3); batches are not supported')
     try:
-        return mesh.winding(pts)
+        return _mesh_winding(mesh, pts)
     finally:
-        mesh.close()
+        if own:
+            mesh.close()
 
 
 def moller_trumbore(ray_o: torch.Tensor, ray_d: torch.Tensor, tris: torch.Tensor, engine=None):
@@ -288,9 +349,9 @@ def raycast_maps(ray_o: torch.Tensor, ray_d: torch.Tensor, verts: torch.Tensor, 
                    norm_map=torch.where(found[:, None], nrm, zero).view(*lead, 3), face=hit.face.view(*lead))
 
 
-def winding_number_nooom(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, quota_GB: float = 15.0, engine=None) -> torch.Tensor:
+def winding_number_nooom(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, quota_GB: float = 15.0, engine=None, mesh=None) -> torch.Tensor:
     """winding_number: the kernel holds one running sum per point, so there is nothing to chunk; the quota is accepted and unused"""
-    return winding_number(pts, verts, faces, engine=engine)
+    return winding_number(pts, verts, faces, engine=engine, mesh=mesh)
 
 
 def winding_shift(winding: torch.Tensor, level_set: float = 0.5, winding_th: float = 0.45) -> torch.Tensor:
@@ -301,16 +362,22 @@ def winding_shift(winding: torch.Tensor, level_set: float = 0.5, winding_th: flo
     return shift
 
 
-def winding_distance(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, winding_th: float = 0.45, engine=None) -> torch.Tensor:
+def winding_distance(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, winding_th: float = 0.45, engine=None, mesh=None) -> torch.Tensor:
     """pts (N,3) -> (N,) the signed distance to the mesh, positive INSIDE: the closest-point distance times the clamped winding sign.
-    One mesh is built and serves both queries."""
-    _check_mesh_args('winding_distance', pts, verts, faces)
-    mesh = _engine(engine).mesh(verts, faces)
+    One mesh is built and serves both queries.  Differentiable in pts: 2 d grad(w) where the shift is neither clipped nor snapped
+    (exactly 0 elsewhere), plus shift grad(d)."""
+    own = mesh is None
+    if own:
+        _check_mesh_args('winding_distance', pts, verts, faces)
+        mesh = _engine(engine).mesh(verts, faces)
+    elif pts.ndim != 2:
+        raise ValueError('winding_distance: pts (N,3); batches are not supported')
     try:
-        d = mesh.closest(pts, want=('d2',)).d2.sqrt()
-        return winding_shift(mesh.winding(pts), 0.5, winding_th) * d
+        d = _mesh_distance(mesh, pts)
+        return winding_shift(_mesh_winding(mesh, pts), 0.5, winding_th) * d
     finally:
-        mesh.close()
+        if own:
+            mesh.close()
 
 
 def winding_distance_remesh(verts: torch.Tensor, faces: torch.Tensor, guide_verts: torch.Tensor = None, guide_faces: torch.Tensor = None,
@@ -585,3 +652,42 @@ def bidirectional_icp_fitting(v0: torch.Tensor, f0: torch.Tensor, v1: torch.Tens
         if verbose and i % int(ep_iter) == 0:
             print(f'bidirectional L2 loss: {loss.item():.5g}')
     return tuple(M[k].solve(p[k].detach(), x0=verts[k]) for k in range(2))
+
+
+def _sum_of_squares(x, y):
+    return (x - y).pow(2).sum()
+
+
+def isosurface_fitting(src_verts: torch.Tensor, src_faces: torch.Tensor, tar_verts: torch.Tensor, tar_faces: torch.Tensor, f=winding_distance,
+                       l=_sum_of_squares, param_lambda: int = 29, thresh: float = 0.5, opt_iter: int = 100, chunk_size: int = 1600, lr: float = 1e-3,
+                       generator: torch.Generator = None, engine=None):
+    """lib/utils/mesh_utils.py:1018-1058: pull the source mesh onto the level set f == thresh of the target's field.  The source is
+    parameterised by u = (I + param_lambda L) v (relightableavatar_amd.largesteps) and optimised with AdamUniform on l(f(query),
+    thresh), query being chunk_size vertices drawn per iteration by torch.randperm with `generator` (on the generator's device; the
+    engine's without one).  f: winding_distance (level set 0: the surface), winding_number (0.5) or any function of (pts, verts, faces,
+    engine=, mesh=) that is differentiable in pts.  ONE target mesh is built for the whole fit and handed to f as mesh=, where the
+    reference's f rebuilds its structures per iteration; the solves are warm-started from the previous vertices; there is no progress
+    bar and nothing is read back.  Returns the float32 vertices (V,3) on the device."""
+    from . import largesteps
+    eng = _engine(engine)
+    dev = eng.device
+    verts = src_verts.detach().to(dev, torch.float32).contiguous()
+    if verts.ndim != 2 or verts.shape[-1] != 3:
+        raise ValueError('isosurface_fitting: src_verts (V,3); batches are not supported')
+    M = largesteps.compute_matrix(verts, src_faces.detach().to('cpu', torch.int32).reshape(-1, 3).contiguous(), param_lambda, engine=eng)
+    param = largesteps.to_differential(M, verts).detach().requires_grad_()
+    optim = largesteps.AdamUniform([param], lr=lr, engine=eng)
+    perm_dev = dev if generator is None else generator.device
+    target = eng.mesh(tar_verts.detach(), tar_faces)
+    try:
+        for _ in range(int(opt_iter)):
+            w = largesteps.from_differential(M, param, 'Cholesky', x0=verts)
+            verts = w.detach()
+            query = w[torch.randperm(len(w), device=perm_dev, generator=generator)[:chunk_size].to(dev)]
+            loss = l(f(query, tar_verts, tar_faces, engine=eng, mesh=target), thresh)
+            optim.zero_grad(set_to_none=True)
+            loss.backward()
+            optim.step()
+    finally:
+        target.close()
+    return M.solve(param.detach(), x0=verts)
