@@ -928,6 +928,50 @@ int ra_cloth_inertia(ra_ctx* ctx, const float* mass_dev, const float* x_next_dev
 /* test hook: elements per workgroup of 0 the face kernel, 1 the hinge kernel, 2 the vertex kernel; 3 elements per chunk of an energy sum */
 int ra_cloth_tile(int which);
 
+/* ---- mesh rasterisation: what the reference's lib/utils/raster_utils.py asks of nvdiffrast (rasterize, interpolate), with gradients ----
+ * Homogeneous (clipless) rasterisation of B views of one face list.  pos_dev: B x n_verts x 4 fp32 clip-space (x, y, z, w);
+ * faces_dev: n_faces x 3 int32, shared by the views.  Pixel (ix, iy) is sampled at NDC ((2 ix + 1) / W - 1, (2 iy + 1) / H - 1): row 0
+ * is at y = -1.  The rule of a (pixel, face) pair — canonical per-edge edge functions, the tie rule on an edge, the face's pixel box,
+ * perspective-correct barycentrics, w > 0 and -1 <= z/w <= 1 — is csrc/ra_raster_rules.hpp's, one named fp32 operation per rounding;
+ * two faces that share an edge decide a sample on it from the same bits, so a consistently oriented mesh has neither cracks nor
+ * doubly owned pixels along interior edges.  Per pixel the lexicographic minimum of (z/w, face index) wins: the maps are a function of
+ * the pixel and the mesh alone, bit for bit, not of the launch or of the order in which faces are met.
+ *   uv_dev B x H x W x 2 fp32 (the barycentrics of corners 0 and 1), zw_dev B x H x W fp32, face_dev B x H x W int32 (-1: empty;
+ *   uv and zw hold 0 there).
+ * Set-up per (view, face), deterministic binning into 8 x 8-pixel tiles (sum, keys, radix sort), one wave per tile.  ONE blocking
+ * read-back per call, 8 bytes: the (tile, face) pair count, which sizes the key buffers, and the face-index verdict; everything else
+ * is asynchronous on the stream.  RA_RASTER_BRUTE scans every face per pixel without binning: the same bits (it still reads the
+ * verdict back).  n_faces == 0 launches nothing and returns empty maps.  Scratch belongs to the ctx.
+ * Errors: "null argument", "bad sizes" (B, H, W >= 1, B x H x W < 2^31, n_faces < 2^24, B x n_faces < 2^31, fewer than 2^31 pairs),
+ * "unknown flag", "face index" (an index outside [0, n_verts), found on the device). */
+enum { RA_RASTER_BRUTE = 1 };
+int ra_rasterize(ra_ctx* ctx, const float* pos_dev, int B, int n_verts, const int* faces_dev, int n_faces, int H, int W, int flags, float* uv_dev,
+                 float* zw_dev, int* face_dev, void* stream);
+/* out[b, y, x, :] = (u a_0 + v a_1) + ((1 - u) - v) a_2 over the A (1..64) channels of the pixel's face's corners, 0 where the pixel
+ * is empty.  attr_dev: n_verts x A fp32 shared by the views (per_view == 0) or B x n_verts x A.  A face id outside [0, n_faces) or a
+ * vertex index outside [0, n_verts) gives 0 at that pixel (ra_rasterize is the call that reports indices).  Asynchronous, no read-back.
+ * Errors: "null argument", "bad sizes". */
+int ra_interpolate(ra_ctx* ctx, const float* attr_dev, int per_view, int n_verts, int A, const int* faces_dev, int n_faces, const float* uv_dev,
+                   const int* face_dev, int B, int H, int W, float* out_dev, void* stream);
+/* The backward passes.  Both read the faces from a topology of the same face list (ra_topo_create, whose build checked them) and use
+ * its vertex -> half-edge lists; the face map is held fixed and zw and face carry no gradient, as in nvdiffrast.
+ * ra_interpolate_backward: dout_dev B x H x W x A -> dattr_dev (nullable; n_verts x A summed over the views when the attributes are
+ * shared, else B x n_verts x A) and duv_dev (nullable; B x H x W x 2, 0 where empty).
+ * ra_rasterize_backward: duv_dev B x H x W x 2 -> dpos_dev B x n_verts x 4, the gradient of the computed (u, v) in the clip-space
+ * positions (the z component is 0).
+ * Reduction order: no float atomics.  The pixels are grouped by (view, face) with one radix sort; one wave per (view, face) adds its
+ * pixels in ascending order per lane and the lanes in a fixed tree, writes corner gradients to scratch, and a vertex pass adds a
+ * vertex's corners in ascending half-edge order (shared attributes: each view's sum, the views ascending).  Every output row is a
+ * function of its inputs alone, bit for bit; row b of dpos does not depend on the other views.  Asynchronous, no read-back.
+ * Errors: "null argument", "bad sizes", "not a topology of this ctx". */
+int ra_interpolate_backward(ra_ctx* ctx, const ra_topo* topo, const float* attr_dev, int per_view, int n_verts, int A, const float* uv_dev,
+                            const int* face_dev, int B, int H, int W, const float* dout_dev, float* dattr_dev, float* duv_dev, void* stream);
+int ra_rasterize_backward(ra_ctx* ctx, const ra_topo* topo, const float* pos_dev, int B, int n_verts, int H, int W, const float* uv_dev,
+                          const int* face_dev, const float* duv_dev, float* dpos_dev, void* stream);
+/* test hook: 0 pixels per tile edge (a tile is one wave), 1 elements per workgroup of the set-up, interpolation and vertex kernels,
+ * 2 the largest channel count */
+int ra_raster_tile(int which);
+
 /* ---- mesh extraction: the two steps the reference's mesh renderer leaves to mcubes and trimesh (mesh_renderer.py:74-84) ----
  * ra_marching_cubes: classic marching cubes on a DEVICE volume of nx x ny x nz fp32 values, x slowest (what reshape gives), with the
  * classic corner and edge numbering, 256-entry tables derived by rule (relightableavatar_amd/mcubes_tables.py) and linear

@@ -16,6 +16,7 @@ RA_WINDING_ONE_PASS, RA_WINDING_SPLIT = 1, 2      # flags of ra_mesh_winding and
 RA_RAYCAST_BRUTE, RA_RAYCAST_UNSORTED = 1, 2      # flags of ra_mesh_raycast
 # the arrays of ra_topo_array, in the header's order
 RA_TOPO_ARRAYS = ('vert', 'twin', 'edge', 'edges', 'edge_counts', 'edge_he_start', 'edge_he', 'nbr_start', 'nbr', 'out_start', 'out_he')
+RA_RASTER_BRUTE = 1      # flag of ra_rasterize
 RA_CLOTH_STRETCH, RA_CLOTH_BENDING, RA_CLOTH_GRAVITY = 1, 2, 4      # terms of ra_cloth_energy
 # the fields of ra_cloth_material in the header's order, with the reference's StVKMaterial defaults
 CLOTH_MATERIAL_DEFAULTS = (('density', 426 * 0.00047), ('thickness', 0.00047), ('young_modulus', 0.7e5), ('poisson_ratio', 0.485),
@@ -209,6 +210,13 @@ SYMBOLS = {
     'ra_cloth_energy': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ra_cloth_inertia': (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float)] + [C.c_void_p] * 5),
     'ra_cloth_tile': (C.c_int, [C.c_int]),
+    'ra_rasterize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    'ra_interpolate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_void_p]),
+    'ra_interpolate_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] +
+                                [C.c_void_p] * 4),
+    'ra_rasterize_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    'ra_raster_tile': (C.c_int, [C.c_int]),
     'ra_ray_tri_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     'ra_sdf_volume': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                 C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

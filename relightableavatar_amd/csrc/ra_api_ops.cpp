@@ -6,6 +6,7 @@
 #include "ra_topo_rules.hpp"
 #include "ra_fit_rules.hpp"
 #include "ra_cloth_rules.hpp"
+#include "ra_raster_rules.hpp"
 #include <cmath>
 #include <cstring>
 
@@ -1204,6 +1205,161 @@ int ra_cloth_inertia(ra_ctx* c, const float* mass, const float* x_next, const fl
     j.part = c->buf<double>("cloth_part", (size_t)rows * (((size_t)V + CLOTH_CHUNK - 1) / CLOTH_CHUNK) + 1, &err);
     RA_CHECK(!err, "ra_cloth_inertia: out of device memory");
     launch_cloth_inertia(j, value, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- mesh rasterisation (ra_raster.hip) -----------------------------------------------------------
+int ra_raster_tile(int which) { return which == 0 ? RASTER_TILE : which == 1 ? RASTER_BLOCK : which == 2 ? RASTER_MAX_CHANNELS : 0; }
+
+static bool raster_sizes_ok(int B, int H, int W) { return B >= 1 && H >= 1 && W >= 1 && (long long)B * H * W < (1ll << 31); }
+
+int ra_rasterize(ra_ctx* c, const float* pos, int B, int V, const int* faces, int F, int H, int W, int flags, float* uv, float* zw, int* face,
+                 void* stream) {
+    // sizes and flags first: they need no ctx, so a caller's mistake is named before anything is dereferenced or launched
+    RA_CHECK(raster_sizes_ok(B, H, W) && V >= 0 && V < (1 << 29) && F >= 0 && F < RASTER_MAX_FACES && (long long)B * F < (1ll << 31) - 1 && (V > 0 || F == 0),
+             "ra_rasterize: bad sizes (B, H, W >= 1, B x H x W < 2^31, F < 2^24, B x F < 2^31; faces need vertices)");
+    RA_CHECK((flags & ~RA_RASTER_BRUTE) == 0, "ra_rasterize: unknown flag");
+    RA_CHECK(c && uv && zw && face, "ra_rasterize: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    const size_t n_pix = (size_t)B * H * W;
+    if (F == 0) {               // empty maps: nothing is launched
+        RA_HIP(hipMemsetAsync(uv, 0, n_pix * 2 * sizeof(float), s));
+        RA_HIP(hipMemsetAsync(zw, 0, n_pix * sizeof(float), s));
+        RA_HIP(hipMemsetAsync(face, 0xff, n_pix * sizeof(int), s));
+        return 0;
+    }
+    RA_CHECK(pos && faces, "ra_rasterize: null argument (pos, faces)");
+    const bool brute = (flags & RA_RASTER_BRUTE) != 0;
+    const size_t n = (size_t)B * F;
+    RasterJob j{};
+    j.pos = pos; j.faces = faces; j.B = B; j.V = V; j.F = F; j.H = H; j.W = W; j.uv = uv; j.zw = zw; j.face = face;
+    int err = 0;
+    j.recs = c->buf<float4>("raster_recs", n * 5, &err);
+    j.stat = c->buf<int>("raster_stat", 2, &err);
+    if (!brute) {
+        j.temp_bytes = raster_temp_bytes((long long)n + 1, 0);
+        j.counts = c->buf<unsigned long long>("raster_counts", n + 1, &err);
+        j.off = c->buf<unsigned long long>("raster_off", n + 1, &err);
+        j.temp = c->buf<char>("raster_tmp", j.temp_bytes + 16, &err);
+    }
+    RA_CHECK(!err, "ra_rasterize: out of device memory");
+    RA_HIP(hipMemsetAsync(j.stat, 0, 2 * sizeof(int), s));
+    RA_CHECK(launch_raster_setup(j, s) == 0, "ra_rasterize: device scan failed");
+    RA_HIP(hipGetLastError());
+    int stat[2] = {};           // the one read-back: the (tile, face) pair count, which sizes the keys, and the face-index verdict
+    RA_HIP(hipMemcpyAsync(stat, j.stat, sizeof(stat), hipMemcpyDeviceToHost, s));
+    RA_HIP(hipStreamSynchronize(s));
+    RA_CHECK(stat[1] == 0, "ra_rasterize: face index outside [0, n_verts)");
+    long long n_pairs = -1;
+    if (!brute) {
+        n_pairs = stat[0];
+        RA_CHECK(n_pairs < 0x7fffffff, "ra_rasterize: bad sizes (2^31 or more (tile, face) pairs)");
+        j.temp_bytes = raster_temp_bytes(0, n_pairs);
+        j.keys = c->buf<unsigned long long>("raster_keys", (size_t)n_pairs + 1, &err);
+        j.keys_sorted = c->buf<unsigned long long>("raster_keys_sorted", (size_t)n_pairs + 1, &err);
+        j.temp = c->buf<char>("raster_sort_tmp", j.temp_bytes + 16, &err);
+        RA_CHECK(!err, "ra_rasterize: out of device memory");
+    }
+    RA_CHECK(launch_raster_tiles(j, n_pairs, s) == 0, "ra_rasterize: device sort failed");
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_interpolate(ra_ctx* c, const float* attr, int per_view, int V, int A, const int* faces, int F, const float* uv, const int* face, int B, int H, int W,
+                   float* out, void* stream) {
+    RA_CHECK(raster_sizes_ok(B, H, W) && V >= 0 && V < (1 << 29) && F >= 0 && F < RASTER_MAX_FACES && A >= 1 && A <= RASTER_MAX_CHANNELS &&
+             (long long)B * V * A < (1ll << 40), "ra_interpolate: bad sizes (B, H, W >= 1, B x H x W < 2^31, F < 2^24, 1 <= A <= 64)");
+    RA_CHECK(c && out, "ra_interpolate: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    if (F == 0 || V == 0) {
+        RA_HIP(hipMemsetAsync(out, 0, (size_t)B * H * W * A * sizeof(float), s));
+        return 0;
+    }
+    RA_CHECK(attr && faces && uv && face, "ra_interpolate: null argument (attr, faces, uv, face)");
+    InterpJob j{};
+    j.attr = attr; j.faces = faces; j.uv = uv; j.face = face; j.B = B; j.V = V; j.F = F; j.H = H; j.W = W; j.A = A; j.per_view = per_view != 0; j.out = out;
+    launch_interpolate(j, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+// the pixels of every (view, face) in ascending order, for the two backward passes
+static int raster_pixel_runs(ra_ctx* c, const int* face, int B, int F, int H, int W, unsigned long long** sorted, hipStream_t s) {
+    const size_t n = (size_t)B * H * W;
+    int err = 0;
+    const size_t tb = raster_temp_bytes(0, (long long)n);
+    unsigned long long* keys = c->buf<unsigned long long>("raster_pix_keys", n, &err);
+    *sorted = c->buf<unsigned long long>("raster_pix_sorted", n, &err);
+    void* temp = c->buf<char>("raster_sort_tmp", tb + 16, &err);
+    if (err) return 1;
+    return launch_raster_pixel_sort(face, B, F, H, W, keys, *sorted, temp, tb, s) ? 2 : 0;
+}
+
+int ra_interpolate_backward(ra_ctx* c, const ra_topo* topo, const float* attr, int per_view, int V, int A, const float* uv, const int* face, int B, int H,
+                            int W, const float* dout, float* dattr, float* duv, void* stream) {
+    RA_CHECK(raster_sizes_ok(B, H, W) && V >= 0 && A >= 1 && A <= RASTER_MAX_CHANNELS,
+             "ra_interpolate_backward: bad sizes (B, H, W >= 1, B x H x W < 2^31, 1 <= A <= 64)");
+    RA_CHECK(c && topo && (dattr || duv), "ra_interpolate_backward: null argument");
+    RA_CHECK(find_topo(c, topo), "ra_interpolate_backward: not a topology of this ctx");
+    const TopoView& t = topo->view;
+    RA_CHECK(raster_sizes_ok(B, H, W) && V == t.n_verts && t.n_faces < RASTER_MAX_FACES && A >= 1 && A <= RASTER_MAX_CHANNELS &&
+             (long long)B * t.n_faces < (1ll << 31) - 1 && (long long)B * t.n_faces * 3 * A < (1ll << 40),
+             "ra_interpolate_backward: bad sizes (B, H, W >= 1, B x H x W < 2^31, n_verts of the topology, F < 2^24, B x F < 2^31, 1 <= A <= 64)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    const size_t n_pix = (size_t)B * H * W;
+    if (t.n_faces == 0 || V == 0) {
+        if (dattr && V > 0) RA_HIP(hipMemsetAsync(dattr, 0, (size_t)(per_view ? B : 1) * V * A * sizeof(float), s));
+        if (duv) RA_HIP(hipMemsetAsync(duv, 0, n_pix * 2 * sizeof(float), s));
+        return 0;
+    }
+    RA_CHECK(attr && uv && face && dout, "ra_interpolate_backward: null argument (attr, uv, face, dout)");
+    InterpJob j{};
+    j.attr = attr; j.faces = t.vert; j.uv = uv; j.face = face; j.B = B; j.V = V; j.F = t.n_faces; j.H = H; j.W = W; j.A = A; j.per_view = per_view != 0;
+    unsigned long long* sorted = nullptr;
+    float* g_face = nullptr;
+    if (dattr) {
+        int err = 0;
+        g_face = c->buf<float>("raster_g_face", (size_t)B * t.n_faces * 3 * A, &err);
+        RA_CHECK(!err, "ra_interpolate_backward: out of device memory");
+        const int rc = raster_pixel_runs(c, face, B, t.n_faces, H, W, &sorted, s);
+        RA_CHECK(rc != 1, "ra_interpolate_backward: out of device memory");
+        RA_CHECK(rc == 0, "ra_interpolate_backward: device sort failed");
+    }
+    launch_interpolate_backward(j, t, sorted, dout, g_face, dattr, duv, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_rasterize_backward(ra_ctx* c, const ra_topo* topo, const float* pos, int B, int V, int H, int W, const float* uv, const int* face, const float* duv,
+                          float* dpos, void* stream) {
+    RA_CHECK(raster_sizes_ok(B, H, W) && V >= 0, "ra_rasterize_backward: bad sizes (B, H, W >= 1, B x H x W < 2^31)");
+    RA_CHECK(c && topo && dpos, "ra_rasterize_backward: null argument");
+    RA_CHECK(find_topo(c, topo), "ra_rasterize_backward: not a topology of this ctx");
+    const TopoView& t = topo->view;
+    RA_CHECK(raster_sizes_ok(B, H, W) && V == t.n_verts && V < (1 << 29) && t.n_faces < RASTER_MAX_FACES && (long long)B * t.n_faces < (1ll << 31) - 1,
+             "ra_rasterize_backward: bad sizes (B, H, W >= 1, B x H x W < 2^31, n_verts of the topology, F < 2^24, B x F < 2^31)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    if (V == 0) return 0;
+    if (t.n_faces == 0) {
+        RA_HIP(hipMemsetAsync(dpos, 0, (size_t)B * V * 4 * sizeof(float), s));
+        return 0;
+    }
+    RA_CHECK(pos && uv && face && duv, "ra_rasterize_backward: null argument (pos, uv, face, duv)");
+    int err = 0;
+    float* g_face = c->buf<float>("raster_g_face", (size_t)B * t.n_faces * 9, &err);
+    RA_CHECK(!err, "ra_rasterize_backward: out of device memory");
+    unsigned long long* sorted = nullptr;
+    const int rc = raster_pixel_runs(c, face, B, t.n_faces, H, W, &sorted, s);
+    RA_CHECK(rc != 1, "ra_rasterize_backward: out of device memory");
+    RA_CHECK(rc == 0, "ra_rasterize_backward: device sort failed");
+    RasterBwdJob j{};
+    j.pos = pos; j.uv = uv; j.duv = duv; j.B = B; j.H = H; j.W = W; j.dpos = dpos;
+    launch_rasterize_backward(j, t, sorted, g_face, s);
     RA_HIP(hipGetLastError());
     return 0;
 }

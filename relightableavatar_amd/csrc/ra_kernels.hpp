@@ -415,6 +415,46 @@ void launch_cloth_build(const TopoView& t, const ClothBuild& b, hipStream_t s);
 void launch_cloth_energy(const TopoView& t, const ClothJob& j, double* energy, hipStream_t s);
 void launch_cloth_inertia(const InertiaJob& j, double* value, hipStream_t s);
 
+// Mesh rasterisation (ra_raster.hip): face records, (tile, face) binning, one wave per 8 x 8 tile; attribute interpolation; both backwards
+constexpr int RASTER_BLOCK = 256;                // (view, face) / (pixel, channel) / (view, vertex) elements per workgroup; the tile and face passes use one wave
+constexpr int RASTER_MAX_FACES = 1 << 24;        // a face id fits the low 24 bits of a (tile, face) key, and survives a float
+constexpr int RASTER_MAX_CHANNELS = 64;
+struct RasterJob {
+    const float* pos;               // B x V x 4 clip-space positions
+    const int* faces;               // F x 3, checked by the set-up kernel
+    int B, V, F, H, W;
+    float4* recs;                   // B x F x 5: the face records (ra_raster_rules.hpp)
+    unsigned long long *counts, *off;       // B F + 1 each: tiles per (view, face) and their exclusive sum; counts == nullptr: no binning
+    unsigned long long *keys, *keys_sorted; // the (tile, face) pairs
+    int* stat;                      // 2: the pair count (saturated), the index flag; zero on entry
+    void* temp;
+    size_t temp_bytes;
+    float *uv, *zw;                 // B x H x W x 2, B x H x W
+    int* face;                      // B x H x W
+};
+struct InterpJob {
+    const float* attr;              // V x A, or B x V x A with per_view
+    const int* faces;               // F x 3
+    const float* uv;
+    const int* face;
+    int B, V, F, H, W, A, per_view;
+    float* out;                     // B x H x W x A (forward only)
+};
+struct RasterBwdJob {
+    const float *pos, *uv, *duv;    // B x V x 4, B x H x W x 2 twice
+    int B, H, W;
+    float* dpos;                    // B x V x 4
+};
+size_t raster_temp_bytes(long long n_scan, long long n_sort);
+int launch_raster_setup(const RasterJob& j, hipStream_t s);
+int launch_raster_tiles(const RasterJob& j, long long n_pairs, hipStream_t s);
+void launch_interpolate(const InterpJob& j, hipStream_t s);
+int launch_raster_pixel_sort(const int* face, int B, int F, int H, int W, unsigned long long* keys, unsigned long long* keys_sorted, void* temp,
+                             size_t temp_bytes, hipStream_t s);
+void launch_interpolate_backward(const InterpJob& j, const TopoView& t, const unsigned long long* keys_sorted, const float* dout, float* g_face, float* dattr,
+                                 float* duv, hipStream_t s);
+void launch_rasterize_backward(const RasterBwdJob& j, const TopoView& t, const unsigned long long* keys_sorted, float* g_face, hipStream_t s);
+
 // scatter hit-slot maps into full-ray outputs (zeros elsewhere), optional premultiplication by acc
 // src_full: src is indexed by ray (like dst) instead of by hit slot
 void launch_scatter_maps(const int* hit_idx, const int* hit_count, int P, int premultiply, const float* acc_full,

@@ -963,6 +963,84 @@ class Engine:
         check(self.lib.ra_topo_create(self.ctx, _ptr(f) if f.shape[0] else None, f.shape[0], int(n_verts), C.byref(handle), self.stream), 'ra_topo_create')
         return Topology(self, handle)
 
+    @staticmethod
+    def _raster_maps(who, raster, device):
+        uv, face = _f32(raster.uv, device), raster.face.detach().to(device=device, dtype=torch.int32).contiguous()
+        if uv.ndim != 4 or uv.shape[3] != 2 or face.shape != uv.shape[:3]:
+            raise ValueError(f'{who}: raster.uv must be (B, H, W, 2) and raster.face (B, H, W)')
+        return uv, face
+
+    def rasterize(self, pos_clip, faces, H, W, brute=False):
+        """pos_clip (B,V,4) or (V,4) clip-space (x, y, z, w), faces (F,3) integer shared by the views -> dotdict on the device
+        (include/relightableavatar.h: ra_rasterize): uv (B,H,W,2) float32 the barycentrics of corners 0 and 1, zw (B,H,W) float32,
+        face (B,H,W) int32, -1 where the pixel is empty (uv and zw hold 0 there).  Pixel (ix, iy) is sampled at NDC
+        ((2 ix + 1) / W - 1, (2 iy + 1) / H - 1), row 0 at y = -1.  brute: scan every face per pixel without binning (the same bits,
+        slower).  One 8-byte read-back per call (the pair count of the binning and the verdict on the face indices)."""
+        pos = _f32(pos_clip, self.device)
+        pos = pos[None] if pos.ndim == 2 else pos
+        if pos.ndim != 3 or pos.shape[2] != 4:
+            raise ValueError('Engine.rasterize: pos_clip must be (B, V, 4) or (V, 4)')
+        f = faces.detach().to(device=self.device, dtype=torch.int32).reshape(-1, 3).contiguous()
+        B, V, H, W = pos.shape[0], pos.shape[1], int(H), int(W)
+        shape = (max(B, 0), max(H, 0), max(W, 0))
+        out = dotdict(uv=torch.empty(*shape, 2, dtype=torch.float32, device=self.device), zw=torch.empty(shape, dtype=torch.float32, device=self.device),
+                      face=torch.empty(shape, dtype=torch.int32, device=self.device))
+        check(self.lib.ra_rasterize(self.ctx, _ptr(pos) if pos.numel() else None, B, V, _ptr(f) if f.numel() else None, f.shape[0], H, W,
+                                    _lib.RA_RASTER_BRUTE if brute else 0, _ptr(out.uv), _ptr(out.zw), _ptr(out.face), self.stream), 'ra_rasterize')
+        return out
+
+    def interpolate(self, attrs, raster, faces):
+        """attrs (V,A) shared by the views or (B,V,A), 1 <= A <= 64; raster: Engine.rasterize's dotdict (uv, face) -> (B,H,W,A) float32
+        on the device, 0 where a pixel is empty (ra_interpolate).  Nothing is read back."""
+        d = self.device
+        a = _f32(attrs, d)
+        uv, face = self._raster_maps('Engine.interpolate', raster, d)
+        B, H, W = face.shape
+        if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[0] != B):
+            raise ValueError(f'Engine.interpolate: attrs must be (V, A) or ({B}, V, A)')
+        f = faces.detach().to(device=d, dtype=torch.int32).reshape(-1, 3).contiguous()
+        V, A = a.shape[-2], a.shape[-1]
+        out = torch.empty(B, H, W, max(A, 0), dtype=torch.float32, device=d)
+        check(self.lib.ra_interpolate(self.ctx, _ptr(a) if a.numel() else None, int(a.ndim == 3), V, A, _ptr(f) if f.numel() else None, f.shape[0], _ptr(uv),
+                                      _ptr(face), B, H, W, _ptr(out), self.stream), 'ra_interpolate')
+        return out
+
+    def interpolate_backward(self, topology, attrs, raster, dout, want=('dattr', 'duv')):
+        """the gradient of Engine.interpolate: dout (B,H,W,A) -> dotdict(dattr shaped like attrs — summed over the views when they are
+        shared —, duv (B,H,W,2)) on the device (ra_interpolate_backward).  topology: Engine.topology of the same faces.  No float
+        atomics: the same bits every time.  Nothing is read back."""
+        d = self.device
+        a, g = _f32(attrs, d), _f32(dout, d)
+        uv, face = self._raster_maps('Engine.interpolate_backward', raster, d)
+        B, H, W = face.shape
+        if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[0] != B) or g.shape != (B, H, W, a.shape[-1]):
+            raise ValueError(f'Engine.interpolate_backward: attrs must be (V, A) or ({B}, V, A) and dout ({B}, {H}, {W}, A)')
+        out = dotdict()
+        if 'dattr' in want:
+            out.dattr = torch.empty_like(a)
+        if 'duv' in want:
+            out.duv = torch.empty_like(uv)
+        check(self.lib.ra_interpolate_backward(self.ctx, topology._handle, _ptr(a) if a.numel() else None, int(a.ndim == 3), a.shape[-2], a.shape[-1], _ptr(uv),
+                                               _ptr(face), B, H, W, _ptr(g), _ptr(out.get('dattr')) if a.numel() else None, _ptr(out.get('duv')), self.stream),
+              'ra_interpolate_backward')
+        return out
+
+    def rasterize_backward(self, topology, pos_clip, raster, duv):
+        """the gradient of Engine.rasterize's uv in the clip-space positions, the face map held fixed: duv (B,H,W,2) -> (B,V,4) float32
+        (ra_rasterize_backward; the z component is 0).  Row b depends on view b alone; the same bits every time.  Nothing is read back."""
+        d = self.device
+        pos = _f32(pos_clip, d)
+        pos = pos[None] if pos.ndim == 2 else pos
+        uv, face = self._raster_maps('Engine.rasterize_backward', raster, d)
+        g = _f32(duv, d)
+        B, H, W = face.shape
+        if pos.ndim != 3 or pos.shape[0] != B or pos.shape[2] != 4 or g.shape != uv.shape:
+            raise ValueError(f'Engine.rasterize_backward: pos_clip must be ({B}, V, 4) and duv ({B}, {H}, {W}, 2)')
+        out = torch.empty_like(pos)
+        check(self.lib.ra_rasterize_backward(self.ctx, topology._handle, _ptr(pos) if pos.numel() else None, B, pos.shape[1], H, W, _ptr(uv), _ptr(face), _ptr(g),
+                                             _ptr(out) if out.numel() else None, self.stream), 'ra_rasterize_backward')
+        return out
+
     def cloth(self, topology, rest_verts, vm, fm, material=None):
         """topology (Engine.topology), rest_verts (V,3), vm (M,2) material coordinates, fm (F,3) integers into vm, material (an
         object or dict with density, thickness, young_modulus, poisson_ratio, bending_multiplier, stretch_multiplier and optionally

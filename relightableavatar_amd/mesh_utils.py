@@ -349,6 +349,33 @@ def raycast_maps(ray_o: torch.Tensor, ray_d: torch.Tensor, verts: torch.Tensor, 
                    norm_map=torch.where(found[:, None], nrm, zero).view(*lead, 3), face=hit.face.view(*lead))
 
 
+def raster_maps(verts: torch.Tensor, faces: torch.Tensor, H: int, W: int, K: torch.Tensor, R: torch.Tensor, T: torch.Tensor, engine=None):
+    """The rasterised twin of raycast_maps: verts (V,3), faces (F,3), the camera's K (3,3), R (3,3), T (3,1) or (3,) -> dotdict on the
+    device: acc_map (H,W,1) 1 where a face covers the pixel, depth_map (H,W,1) the camera z interpolated over the face (0 where empty),
+    norm_map (H,W,3) the face's unit normal normalize((b - a) x (c - a)) in world space (0), face (H,W) int32 (-1).  Engine.rasterize
+    and Engine.interpolate: no box structure is built, so a new pose costs nothing extra.  The rasteriser
+    samples pixel i at the camera pixel coordinate i + 0.5, half a pixel from the integer coordinates Engine.gen_rays casts through
+    (INTEGRATION.md).  Not differentiable: for gradients use raster_utils.rasterize / interpolate."""
+    from .base_utils import dotdict
+    from .raster_utils import get_ndc_perspective_matrix
+    _check_mesh_args('raster_maps', None, verts, faces)
+    eng = _engine(engine)
+    d = eng.device
+    v = verts.detach().to(device=d, dtype=torch.float32)
+    K, R, T = (torch.as_tensor(x).detach().to(device=d, dtype=torch.float32) for x in (K, R, T))
+    cam = v @ R.mT + T.reshape(1, 3)
+    clip = torch.cat([cam, torch.ones_like(cam[:, :1])], dim=-1) @ get_ndc_perspective_matrix(K, H, W).mT
+    rast = eng.rasterize(clip[None], faces, H, W)
+    depth = eng.interpolate(cam[:, 2:3].contiguous(), rast, faces)[0]
+    face = rast.face[0]
+    found = face >= 0
+    tri = v[faces.to(d).long()[face.long().clamp_min(0)]]        # (H,W,3,3)
+    nrm = torch.linalg.cross(tri[..., 1, :] - tri[..., 0, :], tri[..., 2, :] - tri[..., 0, :])
+    nrm = nrm / nrm.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+    zero = torch.zeros((), dtype=torch.float32, device=d)
+    return dotdict(acc_map=found.float()[..., None], depth_map=depth, norm_map=torch.where(found[..., None], nrm, zero), face=face)
+
+
 def winding_number_nooom(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, quota_GB: float = 15.0, engine=None, mesh=None) -> torch.Tensor:
     """winding_number: the kernel holds one running sum per point, so there is nothing to chunk; the quota is accepted and unused"""
     return winding_number(pts, verts, faces, engine=engine, mesh=mesh)

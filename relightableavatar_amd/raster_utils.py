@@ -1,0 +1,199 @@
+"""The reference's lib/utils/raster_utils.py on the device rasteriser (Engine.rasterize / Engine.interpolate).
+
+The camera helpers are the reference's torch arithmetic.  `rasterize` and `interpolate` are autograd ops over the HIP kernels, first
+order only, in nvdiffrast's layouts.  `render_nvdiffrast` is the reference's ATTRIBUTE path.
+
+Deliberate limits (DESIGN.md sections 6 and 25):
+  * the texture path (uv / img, dr.texture, mip maps, rast_db) raises NotImplementedError;
+  * dr.antialias is not built: render_nvdiffrast skips that step, the soft mask comes from R_S supersampling alone, position gradients
+    flow through the interpolated attributes only and no gradient arises at silhouettes;
+  * no depth peeling, no range mode, no scissor;
+  * the sampling rules are this project's (csrc/ra_raster_rules.hpp), not nvdiffrast's fixed-point snapping.
+"""
+from typing import Union
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from .base_utils import dotdict
+
+
+def get_ndc_perspective_matrix(K: Union[torch.Tensor, np.ndarray], H, W):
+    """K (3,3)-like or (B,...) intrinsics -> the (4,4) or (B,4,4) matrix that takes camera-space points to clip space, the reference's:
+    x, y to [-1, 1] over the image, z_clip = -2 CLIP_NEAR, w = z.  Pixel coordinate c maps to NDC 2 c / W - 1, so the rasteriser's
+    sample of pixel i is the camera pixel coordinate i + 0.5."""
+    CLIP_NEAR = 0.01
+    if isinstance(K, torch.Tensor):
+        ixt = K.new_zeros(K.shape[0], 4, 4) if K.ndim == 3 else K.new_zeros(4, 4)
+    elif isinstance(K, np.ndarray):
+        ixt = np.zeros((K.shape[0], 4, 4), dtype=K.dtype) if K.ndim == 3 else np.zeros((4, 4), dtype=K.dtype)
+    else:
+        raise NotImplementedError('unsupport data type for K conversion')
+    ixt[..., 0, 0] = (K[..., 0, 0]) * 2.0 / W
+    ixt[..., 1, 1] = (K[..., 1, 1]) * 2.0 / H
+    ixt[..., 0, 2] = (K[..., 0, 2] - W / 2.0) * 2.0 / W
+    ixt[..., 1, 2] = (K[..., 1, 2] - H / 2.0) * 2.0 / H
+    ixt[..., 2, 2] = 0
+    ixt[..., 2, 3] = -2 * CLIP_NEAR
+    ixt[..., 3, 2] = 1
+    ixt[..., 3, 3] = 0
+    return ixt
+
+
+def _eye4(like: torch.Tensor):
+    return torch.eye(4, 4, device=like.device)[None].expand(like.shape[0], -1, -1).clone()
+
+
+def make_rotation_y(ry: torch.Tensor):
+    """ry (R,) -> (R,4,4) rotations about y"""
+    Rs = _eye4(ry)
+    siny, cosy = ry.sin(), ry.cos()
+    Rs[:, 0, 0] = cosy
+    Rs[:, 0, 2] = siny
+    Rs[:, 1, 1] = 1.0
+    Rs[:, 2, 0] = -siny
+    Rs[:, 2, 2] = cosy
+    return Rs
+
+
+def make_rotation(rx: torch.Tensor = None, ry: torch.Tensor = None, rz: torch.Tensor = None):
+    """Euler angles (R,) each, a missing one is 0 -> (R,4,4): Rz @ Ry @ Rx"""
+    assert not (rx is None and ry is None and rz is None)
+    not_none = rx if rx is not None else (ry if ry is not None else rz)
+    rx = torch.zeros_like(not_none) if rx is None else rx
+    ry = torch.zeros_like(not_none) if ry is None else ry
+    rz = torch.zeros_like(not_none) if rz is None else rz
+    sinX, sinY, sinZ = rx.sin(), ry.sin(), rz.sin()
+    cosX, cosY, cosZ = rx.cos(), ry.cos(), rz.cos()
+    Rx = _eye4(ry)
+    Rx[:, 1, 1] = cosX
+    Rx[:, 1, 2] = -sinX
+    Rx[:, 2, 1] = sinX
+    Rx[:, 2, 2] = cosX
+    Ry = _eye4(ry)
+    Ry[:, 0, 0] = cosY
+    Ry[:, 0, 2] = sinY
+    Ry[:, 2, 0] = -sinY
+    Ry[:, 2, 2] = cosY
+    Rz = _eye4(ry)
+    Rz[:, 0, 0] = cosZ
+    Rz[:, 0, 1] = -sinZ
+    Rz[:, 1, 0] = sinZ
+    Rz[:, 1, 1] = cosZ
+    return Rz.matmul(Ry).matmul(Rx)
+
+
+def bilinear_interpolation(input: torch.Tensor, shape) -> torch.Tensor:
+    """input (B,H,W,C) -> (B,*shape,C): F.interpolate, bilinear, align_corners=False"""
+    return F.interpolate(input.permute(0, 3, 1, 2), shape, mode='bilinear', align_corners=False).permute(0, 2, 3, 1)
+
+
+def _engine(engine):
+    from .mesh_utils import _engine as get
+    return get(engine)
+
+
+def _split(rast):
+    """nvdiffrast's (B,H,W,4) -> the dotdict Engine.interpolate reads"""
+    r = rast.detach()
+    return dotdict(uv=r[..., :2].contiguous(), zw=r[..., 2].contiguous(), face=(r[..., 3] - 1).to(torch.int32).contiguous())
+
+
+class _Rasterize(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, faces, H, W, engine, topology):
+        out = engine.rasterize(pos, faces, H, W)
+        rast = torch.cat([out.uv, out.zw[..., None], (out.face + 1).float()[..., None]], dim=-1)       # F < 2^24: a face id survives a float
+        ctx.save_for_backward(pos.detach(), rast)
+        ctx.engine, ctx.topology, ctx.faces, ctx.like = engine, topology, faces, (pos.shape, pos.dtype, pos.device)
+        return rast
+
+    @staticmethod
+    def backward(ctx, g):
+        pos, rast = ctx.saved_tensors
+        topo = ctx.topology if ctx.topology is not None else ctx.engine.topology(ctx.faces, pos.shape[-2])
+        shape, dtype, device = ctx.like
+        d = ctx.engine.rasterize_backward(topo, pos, _split(rast), g[..., :2])      # zw and face carry no gradient
+        return d.reshape(shape).to(device=device, dtype=dtype), None, None, None, None, None
+
+
+class _Interpolate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, attrs, rast, faces, engine, topology):
+        out = engine.interpolate(attrs, _split(rast), faces)
+        ctx.save_for_backward(attrs.detach(), rast.detach())
+        ctx.engine, ctx.topology, ctx.faces = engine, topology, faces
+        ctx.like = (attrs.shape, attrs.dtype, attrs.device, rast.dtype, rast.device)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        attrs, rast = ctx.saved_tensors
+        topo = ctx.topology if ctx.topology is not None else ctx.engine.topology(ctx.faces, attrs.shape[-2])
+        want = tuple(k for k, need in zip(('dattr', 'duv'), ctx.needs_input_grad[:2]) if need)
+        a_shape, a_dtype, a_device, r_dtype, r_device = ctx.like
+        d = ctx.engine.interpolate_backward(topo, attrs, _split(rast), g, want=want) if want else dotdict()
+        dattr = d.dattr.reshape(a_shape).to(device=a_device, dtype=a_dtype) if 'dattr' in d else None
+        drast = None
+        if 'duv' in d:
+            drast = torch.cat([d.duv, torch.zeros_like(d.duv)], dim=-1).to(device=r_device, dtype=r_dtype)
+        return dattr, drast, None, None, None
+
+
+def rasterize(pos: torch.Tensor, faces: torch.Tensor, H: int, W: int, engine=None, topology=None) -> torch.Tensor:
+    """pos (B,V,4) clip-space positions, faces (F,3) -> nvdiffrast's (B,H,W,4) float32 on the device: u, v, z/w, face + 1 (0 where the
+    pixel is empty).  Differentiable in pos through u and v with the face map held fixed (first order); z/w and the face carry no
+    gradient.  topology: Engine.topology(faces, V), which the backward needs — built there when not given (one read-back)."""
+    if pos.ndim != 3 or pos.shape[-1] != 4:
+        raise ValueError('rasterize: pos must be (B, V, 4); the range mode is not supported')
+    return _Rasterize.apply(pos, faces, int(H), int(W), _engine(engine), topology)
+
+
+def interpolate(attrs: torch.Tensor, rast: torch.Tensor, faces: torch.Tensor, rast_db=None, diff_attrs=None, engine=None, topology=None) -> torch.Tensor:
+    """attrs (V,A) or (B,V,A), 1 <= A <= 64; rast: rasterize's output -> (B,H,W,A) float32, 0 where the pixel is empty.  Differentiable
+    in attrs and in rast's u, v (first order).  rast_db / diff_attrs (pixel differentials) are not supported."""
+    if rast_db is not None or diff_attrs is not None:
+        raise NotImplementedError('interpolate: pixel differentials (rast_db, diff_attrs) belong to the texture path, which is not supported')
+    return _Interpolate.apply(attrs, rast, faces, _engine(engine), topology)
+
+
+def render_nvdiffrast(verts: torch.Tensor, faces: torch.Tensor, attrs: torch.Tensor = None, uv: torch.Tensor = None, img: torch.Tensor = None,
+                      H: int = 512, W: int = 512, R: torch.Tensor = None, T: torch.Tensor = None, K: torch.Tensor = None, R_S: int = 2,
+                      pos_gradient_boost: float = 1.0, engine=None, topology=None):
+    """The reference's render_nvdiffrast, attribute path: verts (B,V,3|4) or (V,3) with R, faces (F,3), attrs (B,V,A) or (V,A), R (B,3,3),
+    T (B,3,1), K (B,4,4) clip matrix (None: the reference's default) -> (rast_attrs (B,H,W,A), rast_msk (B,H,W)).  One mesh is expanded
+    over the views of R; the maps are rasterised at R_S times the size and resized bilinearly.  dr.antialias is NOT applied (module
+    docstring): the mask is soft through R_S alone and carries no gradient; pos_gradient_boost is accepted and unused.
+    uv / img (the texture path) raise NotImplementedError."""
+    if uv is not None or img is not None:
+        raise NotImplementedError('render_nvdiffrast: the texture path (uv, img: dr.texture, mip maps, rast_db) is not supported')
+    assert attrs is not None
+    assert int(R_S) == R_S
+    if verts.ndim == 2 and R is not None:
+        verts = verts[None].expand(R.shape[0], *verts.shape)
+    if attrs.ndim == 2 and R is not None:
+        attrs = attrs[None].expand(R.shape[0], *attrs.shape)
+    verts = verts.float().contiguous()
+    attrs = attrs.float().contiguous()
+    faces = faces.int().contiguous()
+    A = attrs.shape[-1]
+    if R is not None and T is not None:
+        vverts = verts @ R.mT + T.mT
+        homovverts = torch.cat([vverts, vverts.new_ones((*vverts.shape[:-1], 1))], dim=-1)
+    elif verts.shape[-1] == 3:
+        homovverts = torch.cat([verts, verts.new_ones((*verts.shape[:-1], 1))], dim=-1)
+    else:
+        homovverts = verts
+    if K is None:
+        K = get_ndc_perspective_matrix(torch.tensor([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, -2 * 0.001], [0, 0, 1, 0]], device=verts.device, dtype=verts.dtype), H, W)
+    ndcverts = homovverts @ K.mT
+    R_S = int(R_S)
+    R_H, R_W = int(H * R_S), int(W * R_S)
+    rast = rasterize(ndcverts, faces, R_H, R_W, engine=engine, topology=topology)
+    rend_msk = rast[:, :, :, 3] != 0
+    pattrs = interpolate(attrs, rast, faces, engine=engine, topology=topology)
+    aa = torch.cat([pattrs, rend_msk.view(rast.shape[0], R_H, R_W, 1).to(pattrs.dtype)], dim=-1)
+    aa = bilinear_interpolation(aa, [H, W])
+    rast_attrs, rast_msk = aa.split([A, 1], dim=-1)
+    return rast_attrs, rast_msk[..., 0]

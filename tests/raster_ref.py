@@ -1,0 +1,314 @@
+"""Restatements of the rasteriser's rule (relightableavatar_amd/csrc/ra_raster_rules.hpp) for the tests.
+
+  raster(pos, faces, H, W, np.float32)   the kernel's operations in the kernel's order, one numpy float32 operation per rounding:
+                                         what ra_rasterize must equal bit for bit
+  raster(pos, faces, H, W, np.float64)   the same rule in float64 over every pixel x every face, without the pixel box (the box is
+                                         conservative, so it changes nothing in exact arithmetic), plus the `decided` mask
+  plain32(...)                           the float32 baseline of the 10 x rule: per-face adjoint coefficients, no named order
+  interp(...), grads_closed(...)         interpolation and the closed-form gradients the kernels use, in either precision
+  grads_autograd(...)                    torch autograd through the float64 (or float32) barycentrics with the face map held fixed
+The clip-space positions are float32 inputs; every restatement starts from the same float32 values.
+"""
+import functools
+
+import numpy as np
+
+BARY_FLOOR, BARY_NEAR = -1e-3, 1e-4         # the `decided` classification
+
+
+# ---- meshes and cameras ---------------------------------------------------------------------------------------------------------------
+def uv_sphere(stacks=12, slices=16, radius=0.5):
+    """(2 + (stacks - 1) slices) vertices, 2 slices (stacks - 1) faces, outward; the poles have valence `slices`"""
+    v = [(0.0, radius, 0.0)]
+    for i in range(1, stacks):
+        th = np.pi * i / stacks
+        for j in range(slices):
+            ph = 2 * np.pi * j / slices
+            v.append((radius * np.sin(th) * np.cos(ph), radius * np.cos(th), radius * np.sin(th) * np.sin(ph)))
+    v.append((0.0, -radius, 0.0))
+    f = []
+    ring = lambda i, j: 1 + (i - 1) * slices + j % slices
+    for j in range(slices):
+        f.append((0, ring(1, j + 1), ring(1, j)))
+        f.append((len(v) - 1, ring(stacks - 1, j), ring(stacks - 1, j + 1)))
+    for i in range(1, stacks - 1):
+        for j in range(slices):
+            a, b, c, d = ring(i, j), ring(i, j + 1), ring(i + 1, j), ring(i + 1, j + 1)
+            f.append((a, b, d))
+            f.append((a, d, c))
+    return np.asarray(v, np.float64), np.asarray(f, np.int32)
+
+
+def camera(H, W, angle=0.6, dist=2.0, focal=1.6):
+    """K (3,3), R (3,3), T (3,): a perspective camera rotated about x and y, looking at the origin from `dist`"""
+    cx, sx, cy, sy = np.cos(0.35), np.sin(0.35), np.cos(angle), np.sin(angle)
+    R = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    K = np.array([[focal * W / 2, 0, W / 2 + 0.3], [0, focal * W / 2, H / 2 - 0.2], [0, 0, 1]])
+    return K, R, np.array([0.02, -0.03, dist])
+
+
+def ndc_matrix(K, H, W, near=0.01):
+    P = np.zeros((4, 4))
+    P[0, 0], P[1, 1] = K[0, 0] * 2.0 / W, K[1, 1] * 2.0 / H
+    P[0, 2], P[1, 2] = (K[0, 2] - W / 2.0) * 2.0 / W, (K[1, 2] - H / 2.0) * 2.0 / H
+    P[2, 3], P[3, 2] = -2 * near, 1
+    return P
+
+
+def clip_positions(verts, K, R, T, H, W):
+    """float32 (V,4) clip-space positions of world vertices"""
+    cam = verts @ R.T + T
+    return (np.concatenate([cam, np.ones_like(cam[:, :1])], 1) @ ndc_matrix(K, H, W).T).astype(np.float32)
+
+
+def sphere_case(H, W, angle=0.6):
+    v, f = uv_sphere()
+    return clip_positions(v, *camera(H, W, angle), H, W), f
+
+
+def lattice_grid(H=16, W=16, n=8, first=4):
+    """n x n quads whose vertices sit exactly on pixel centres first .. first + n, with varying w; every product below is exact"""
+    pos, idx = [], {}
+    for j in range(n + 1):
+        for i in range(n + 1):
+            w = 1.0 + 0.25 * ((3 * i + 5 * j) % 4)
+            x, y = (2 * (first + i) + 1) / W - 1, (2 * (first + j) + 1) / H - 1
+            idx[i, j] = len(pos)
+            pos.append((x * w, y * w, 0.125 * w * (((i + 2 * j) % 3) - 1), w))
+    f = []
+    for j in range(n):
+        for i in range(n):
+            a, b, c, d = idx[i, j], idx[i + 1, j], idx[i, j + 1], idx[i + 1, j + 1]
+            f += [(a, b, d), (a, d, c)] if (i + j) % 2 else [(a, b, c), (b, d, c)]
+    return np.asarray(pos, np.float32), np.asarray(f, np.int32)
+
+
+def triangle_cases():
+    """name -> (pos (V,4) float32, faces): one triangle in all three vertex orders and both windings, one with a vertex at w < 0, a
+    degenerate face beside a good one, 300 faces stacked over one tile"""
+    tri = np.array([[-0.61, -0.52, 0.1, 1.0], [0.73, -0.31, -0.2, 1.3], [0.05, 0.68, 0.3, 0.9]], np.float32)
+    out = {}
+    for name, order in (('tri012', (0, 1, 2)), ('tri120', (1, 2, 0)), ('tri201', (2, 0, 1)), ('tri021', (0, 2, 1)), ('tri210', (2, 1, 0)), ('tri102', (1, 0, 2))):
+        out[name] = (tri, np.array([order], np.int32))
+    behind = tri.copy()
+    behind[2] = (0.3, 0.9, 0.05, -0.4)
+    out['w_negative'] = (behind, np.array([[0, 1, 2]], np.int32))
+    deg = np.concatenate([tri, np.array([[0.2, 0.2, 0.0, 1.0], [0.4, 0.4, 0.0, 2.0], [np.nan, 0.0, 0.0, 1.0]], np.float32)])
+    out['degenerate'] = (deg, np.array([[0, 1, 2], [3, 3, 4], [0, 0, 1], [0, 1, 5], [3, 4, 3]], np.int32))
+    rng = np.random.default_rng(5)
+    pos, f = [], []
+    for k in range(300):            # inside NDC [-0.45, -0.05]^2: pixels 9 .. 14 of 32, one 8 x 8 tile
+        c = rng.uniform(-0.4, -0.1, 2)
+        w = rng.uniform(0.8, 1.5, 3)
+        z = rng.uniform(-0.5, 0.5)
+        for q in range(3):
+            p = c + rng.uniform(-0.05, 0.05, 2)
+            pos.append((p[0] * w[q], p[1] * w[q], z * w[q], w[q]))
+        f.append((3 * k, 3 * k + 1, 3 * k + 2) if k % 2 else (3 * k + 2, 3 * k + 1, 3 * k))
+    out['stacked'] = (np.asarray(pos, np.float32), np.asarray(f, np.int32))
+    return out
+
+
+# ---- the rule -------------------------------------------------------------------------------------------------------------------------
+def centre(i, n, dt):
+    return (2 * np.asarray(i) + 1).astype(dt) / dt(n) - dt(1)
+
+
+def _edge(a, b, dt):
+    return np.array([a[1] * b[3] - a[3] * b[1], a[3] * b[0] - a[0] * b[3], a[0] * b[1] - a[1] * b[0]], dt)
+
+
+def _lo(ndc, n, dt):
+    h = dt(0.5) * dt(n)
+    f = np.floor((ndc * h + h) - dt(1.5))
+    return 0 if not f > 0 else n if f > n else int(f)
+
+
+def _hi(ndc, n, dt):
+    h = dt(0.5) * dt(n)
+    f = np.ceil((ndc * h + h) + dt(0.5))
+    return n - 1 if not f < n - 1 else -1 if f < -1 else int(f)
+
+
+def setup(p, idx, H, W, dt, box=True):
+    """the face record: None for a dropped face, else (c (3,3) canonical triples, neg (3,) bool, back, z, w, box)"""
+    p = [q.astype(dt) for q in p]
+    i0, i1, i2 = (int(i) for i in idx)
+    c, neg = np.zeros((3, 3), dt), np.zeros(3, bool)
+    for k, (ia, ib, a, b) in enumerate(((i1, i2, p[1], p[2]), (i2, i0, p[2], p[0]), (i0, i1, p[0], p[1]))):
+        if ia < ib:
+            c[k] = _edge(a, b, dt)
+        else:
+            c[k], neg[k] = _edge(b, a, dt), True
+    d0 = (c[0, 0] * p[0][0] + c[0, 1] * p[0][1]) + c[0, 2] * p[0][3]
+    det = -d0 if neg[0] else d0
+    if not (det < 0 or det > 0) or not all(np.isfinite(q).all() for q in p):
+        return None
+    bx = (0, 0, W - 1, H - 1)
+    if box and all(q[3] > 0 for q in p):
+        xs, ys = [q[0] / q[3] for q in p], [q[1] / q[3] for q in p]
+        bx = (_lo(min(xs), W, dt), _lo(min(ys), H, dt), _hi(max(xs), W, dt), _hi(max(ys), H, dt))
+    return c, neg, bool(det < 0), np.array([q[2] for q in p], dt), np.array([q[3] for q in p], dt), bx
+
+
+def sample(rec, px, py, ix, iy):
+    """one face over the pixel grid: (inside-and-kept mask, u, v, zw, S, (b0, b1, b2))"""
+    c, neg, back, z, w, bx = rec
+    E = [(c[k, 0] * px + c[k, 1] * py) + c[k, 2] for k in range(3)]
+    ok = (ix >= bx[0]) & (ix <= bx[2]) & (iy >= bx[1]) & (iy <= bx[3])
+    for k in range(3):
+        ok &= (E[k] >= 0) if neg[k] == back else (E[k] < 0)
+    e = [-E[k] if neg[k] else E[k] for k in range(3)]
+    S = (e[0] + e[1]) + e[2]
+    b = [e[k] / S for k in range(3)]
+    zn = (b[0] * z[0] + b[1] * z[1]) + b[2] * z[2]
+    wn = (b[0] * w[0] + b[1] * w[1]) + b[2] * w[2]
+    zw = zn / wn
+    ok &= (wn > 0) & (zw >= -1) & (zw <= 1)
+    return ok, b[0], b[1], zw, S, b
+
+
+def raster(pos, faces, H, W, dt=np.float32):
+    """pos (B,V,4) or (V,4) float32, faces (F,3) -> dict(uv (B,H,W,2), zw (B,H,W), face (B,H,W) int32) in dt; dt = float64 adds
+    `decided` (B,H,W) and `cover` (B,H,W) the number of faces that own each pixel"""
+    pos = pos[None] if pos.ndim == 2 else pos
+    B, f64 = pos.shape[0], dt == np.float64
+    ix, iy = np.meshgrid(np.arange(W), np.arange(H))
+    px, py = centre(ix, W, dt), centre(iy, H, dt)
+    uv, zw, face = np.zeros((B, H, W, 2), dt), np.zeros((B, H, W), dt), np.full((B, H, W), -1, np.int32)
+    cover, fragile = np.zeros((B, H, W), np.int32), np.zeros((B, H, W), bool)
+    with np.errstate(all='ignore'):
+        for b in range(B):
+            for f, idx in enumerate(faces):
+                rec = setup([pos[b, i] for i in idx], idx, H, W, dt, box=not f64)
+                if rec is None:
+                    continue
+                ok, u, v, z, S, bary = sample(rec, px, py, ix, iy)
+                cover[b] += ok
+                if f64:
+                    near = np.isfinite(z) & (bary[0] > BARY_FLOOR) & (bary[1] > BARY_FLOOR) & (bary[2] > BARY_FLOOR)
+                    fragile[b] |= near & ((np.abs(bary[0]) < BARY_NEAR) | (np.abs(bary[1]) < BARY_NEAR) | (np.abs(bary[2]) < BARY_NEAR))
+                take = ok & ((face[b] < 0) | (z < zw[b]) | ((z == zw[b]) & (f < face[b])))
+                uv[b, ..., 0], uv[b, ..., 1] = np.where(take, u, uv[b, ..., 0]), np.where(take, v, uv[b, ..., 1])
+                zw[b], face[b] = np.where(take, z, zw[b]), np.where(take, f, face[b])
+    out = dict(uv=uv, zw=zw, face=face, cover=cover)
+    if f64:
+        out['decided'] = ~fragile
+    return out
+
+
+def plain32(pos, faces, face_map, H, W):
+    """the float32 baseline: u, v, zw of the given face at every covered pixel from the adjugate of [V0 V1 V2], written as numpy
+    expressions with no named order"""
+    pos = (pos[None] if pos.ndim == 2 else pos).astype(np.float32)
+    B = pos.shape[0]
+    ix, iy = np.meshgrid(np.arange(W), np.arange(H))
+    px, py = centre(ix, W, np.float32), centre(iy, H, np.float32)
+    uv, zw = np.zeros((B, H, W, 2), np.float32), np.zeros((B, H, W), np.float32)
+    with np.errstate(all='ignore'):
+        for b in range(B):
+            got = face_map[b] >= 0
+            tri = pos[b][faces[np.maximum(face_map[b], 0)]]         # (H,W,3,4)
+            V = tri[..., [0, 1, 3]]
+            pt = np.stack([px, py, np.ones_like(px)], -1)
+            lam = [(np.cross(V[..., (k + 1) % 3, :], V[..., (k + 2) % 3, :]) * pt).sum(-1) for k in range(3)]
+            s = lam[0] + lam[1] + lam[2]
+            bary = [l / s for l in lam]
+            z = sum(bary[k] * tri[..., k, 2] for k in range(3)) / sum(bary[k] * tri[..., k, 3] for k in range(3))
+            uv[b, ..., 0], uv[b, ..., 1], zw[b] = np.where(got, bary[0], 0), np.where(got, bary[1], 0), np.where(got, z, 0)
+    return dict(uv=uv, zw=zw)
+
+
+def interp(attr, faces, uv, face_map, dt=np.float32):
+    """(B,H,W,A): (u a0 + v a1) + ((1 - u) - v) a2, 0 where empty; attr (V,A) or (B,V,A)"""
+    B = face_map.shape[0]
+    a = np.broadcast_to(attr, (B,) + attr.shape[-2:]).astype(dt)
+    u, v = uv[..., 0:1].astype(dt), uv[..., 1:2].astype(dt)
+    out = np.zeros(face_map.shape + (attr.shape[-1],), dt)
+    for b in range(B):
+        c = a[b][faces[np.maximum(face_map[b], 0)]]         # (H,W,3,A)
+        val = (u[b] * c[..., 0, :] + v[b] * c[..., 1, :]) + ((dt(1) - u[b]) - v[b]) * c[..., 2, :]
+        out[b] = np.where(face_map[b][..., None] >= 0, val, 0)
+    return out
+
+
+def grads_closed(pos, faces, uv, face_map, duv, attr, dout, dt=np.float64):
+    """the closed forms of the kernels in dt, the face map held fixed: dict(dpos (B,V,4) from duv, dattr shaped like attr and
+    duv_interp (B,H,W,2) from dout).  uv is the forward's (in float64: recomputed by the caller in float64)."""
+    pos = (pos[None] if pos.ndim == 2 else pos)
+    B, V = pos.shape[:2]
+    H, W = face_map.shape[1:]
+    ix, iy = np.meshgrid(np.arange(W), np.arange(H))
+    px, py = centre(ix, W, dt), centre(iy, H, dt)
+    shared = attr.ndim == 2
+    a = np.broadcast_to(attr, (B,) + attr.shape[-2:]).astype(dt)
+    dpos, dattr, duv_i = np.zeros((B, V, 4), dt), np.zeros(a.shape, dt), np.zeros(uv.shape, dt)
+    with np.errstate(all='ignore'):
+        for b in range(B):
+            for f in np.unique(face_map[b][face_map[b] >= 0]):
+                idx = faces[f]
+                m = face_map[b] == f
+                c, neg, back, z, w, bx = setup([pos[b, i] for i in idx], idx, H, W, dt, box=False)
+                x, y = px[m], py[m]
+                e = [(-1 if neg[k] else 1) * ((c[k, 0] * x + c[k, 1] * y) + c[k, 2]) for k in range(3)]
+                S = (e[0] + e[1]) + e[2]
+                u, v = uv[b][m][:, 0].astype(dt), uv[b][m][:, 1].astype(dt)
+                du, dv = duv[b][m][:, 0].astype(dt), duv[b][m][:, 1].astype(dt)
+                g = [((du - du * u) - dv * v) / S, ((dv - dv * v) - du * u) / S, -(du * u + dv * v) / S]
+                G = [np.array([(g[k] * x).sum(dtype=dt), (g[k] * y).sum(dtype=dt), g[k].sum(dtype=dt)], dt) for k in range(3)]
+                Vx = [pos[b, i][[0, 1, 3]].astype(dt) for i in idx]
+                corner = [np.cross(G[1], Vx[2]) + np.cross(Vx[1], G[2]), np.cross(G[2], Vx[0]) + np.cross(Vx[2], G[0]),
+                          np.cross(G[0], Vx[1]) + np.cross(Vx[0], G[1])]
+                for k in range(3):
+                    dpos[b, idx[k], [0, 1, 3]] += corner[k].astype(dt)
+                d = dout[b][m].astype(dt)           # (n, A)
+                bary = [u, v, (dt(1) - u) - v]
+                for k in range(3):
+                    dattr[b, idx[k]] += (bary[k][:, None] * d).sum(0, dtype=dt)
+                a0, a1, a2 = (a[b, i] for i in idx)
+                duv_i[b][m] = np.stack([(d * (a0 - a2)).sum(-1, dtype=dt), (d * (a1 - a2)).sum(-1, dtype=dt)], -1)
+    return dict(dpos=dpos, dattr=dattr.sum(0, dtype=dt) if shared else dattr, duv_interp=duv_i)
+
+
+def grads_autograd(pos, faces, face_map, duv, attr, dout, dtype):
+    """torch autograd through plain barycentrics (oriented cross products, torch's own order) with the face map held fixed, in the
+    given torch dtype: the same three gradients, and the uv it computed"""
+    import torch
+    p = torch.tensor(pos[None] if pos.ndim == 2 else pos, dtype=dtype, requires_grad=True)
+    a = torch.tensor(attr, dtype=dtype, requires_grad=True)
+    B, H, W = face_map.shape
+    fm = torch.as_tensor(face_map).long()
+    got = fm >= 0
+    ix, iy = torch.meshgrid(torch.arange(W), torch.arange(H), indexing='xy')
+    px = (2 * ix + 1).to(dtype) / W - 1
+    py = (2 * iy + 1).to(dtype) / H - 1
+    pt = torch.stack([px, py, torch.ones_like(px)], -1).expand(B, H, W, 3)
+    F = torch.as_tensor(faces).long()
+    tri = torch.stack([p[b][F[fm[b].clamp_min(0)]] for b in range(B)])           # (B,H,W,3,4)
+    Vx = tri[..., [0, 1, 3]]
+    lam = [(torch.linalg.cross(Vx[..., (k + 1) % 3, :], Vx[..., (k + 2) % 3, :]) * pt).sum(-1) for k in range(3)]
+    s = lam[0] + lam[1] + lam[2]
+    safe = torch.where(got, s, torch.ones_like(s))
+    u, v = torch.where(got, lam[0] / safe, 0 * s), torch.where(got, lam[1] / safe, 0 * s)
+    uv = torch.stack([u, v], -1)
+    dpos, = torch.autograd.grad((uv * torch.tensor(duv, dtype=dtype)).sum(), p)
+    uvc = uv.detach().clone().requires_grad_(True)
+    ab = a.expand(B, *a.shape[-2:])
+    c = torch.stack([ab[b][F[fm[b].clamp_min(0)]] for b in range(B)])            # (B,H,W,3,A)
+    out = uvc[..., 0:1] * c[..., 0, :] + uvc[..., 1:2] * c[..., 1, :] + (1 - uvc[..., 0:1] - uvc[..., 1:2]) * c[..., 2, :]
+    out = torch.where(got[..., None], out, torch.zeros_like(out))
+    dattr, duv_i = torch.autograd.grad((out * torch.tensor(dout, dtype=dtype)).sum(), (a, uvc))
+    return dict(dpos=dpos.numpy(), dattr=dattr.numpy(), duv_interp=duv_i.numpy(), uv=uv.detach().numpy())
+
+
+@functools.lru_cache(None)
+def sphere_reference(H, W, views=1):
+    """the shared, read-only references of the sphere at one size: pos, faces, the float32 and float64 restatements"""
+    poses = [sphere_case(H, W, 0.6 + 0.9 * k) for k in range(views)]
+    pos, faces = np.stack([p for p, _ in poses]), poses[0][1]
+    out = dict(pos=pos, faces=faces, r32=raster(pos, faces, H, W, np.float32), r64=raster(pos, faces, H, W, np.float64))
+    for d in (out['r32'], out['r64']):
+        for a in d.values():
+            a.setflags(write=False)
+    pos.setflags(write=False)
+    return out

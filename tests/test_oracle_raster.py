@@ -1,0 +1,176 @@
+"""The rasteriser without a GPU:
+    1. the camera helpers of raster_utils equal the golden the reference itself wrote (tests/golden/raster.npz), exactly;
+    2. the float64 restatement of the rule (tests/raster_ref.py) classifies the pixels, and the kernel-order float32 restatement —
+       what ra_rasterize must equal bit for bit on the device — returns the float64 face on every decided pixel, keeps u, v, zw under
+       the 10 x float32 rule against a plain float32 restatement, and owns pixels exactly (closed sphere: 0 or 2; lattice grid: 64 once);
+    3. the closed-form gradients the kernels use match torch autograd in float64 to 1e-9, and in float32 stay under the 10 x rule;
+    4. tests/native/raster_rules_main.cpp: the complementarity lemma and the depth rule's order independence, plain and sanitized;
+    5. argument errors of the four entry points are raised before any launch (no ctx is needed to name them).
+Every test prints its figures before it asserts."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import raster_ref as R
+from frame_stage_ref import parity
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+UNDECIDED_CAP = 0.01
+
+
+def test_camera_helpers_equal_the_reference(golden):
+    from relightableavatar_amd import raster_utils as U
+    g = golden('raster.npz')
+    H, W = int(g['H']), int(g['W'])
+    t = lambda k: torch.from_numpy(g[k].copy())
+    got = {'ndc_K2_torch': U.get_ndc_perspective_matrix(t('K2'), H, W).numpy(), 'ndc_K3_torch': U.get_ndc_perspective_matrix(t('K3'), H, W).numpy(),
+           'ndc_K2_numpy': U.get_ndc_perspective_matrix(g['K2'].copy(), H, W), 'ndc_K3_numpy': U.get_ndc_perspective_matrix(g['K3'].copy(), H, W),
+           'rot_y': U.make_rotation_y(t('ry')).numpy(), 'rot_xyz': U.make_rotation(t('rx'), t('ry'), t('rz')).numpy(),
+           'rot_x': U.make_rotation(rx=t('rx')).numpy(), 'rot_z': U.make_rotation(rz=t('rz')).numpy()}
+    for k, a in got.items():
+        same = a.dtype == g[k].dtype and np.array_equal(a, g[k])
+        print(f'{k}: {a.shape} {a.dtype} equal {same}')
+        assert same, k
+    with pytest.raises(NotImplementedError):
+        U.get_ndc_perspective_matrix([[1.0]], H, W)
+    x = torch.arange(2 * 4 * 6 * 3, dtype=torch.float32).reshape(2, 4, 6, 3)
+    assert torch.equal(U.bilinear_interpolation(x, [2, 3]), torch.nn.functional.interpolate(x.permute(0, 3, 1, 2), [2, 3], mode='bilinear',
+                                                                                            align_corners=False).permute(0, 2, 3, 1))
+
+
+@pytest.mark.parametrize('size', [(64, 64), (37, 53)])
+def test_sphere_classification_and_parity(size):
+    H, W = size
+    ref = R.sphere_reference(H, W)
+    r32, r64 = ref['r32'], ref['r64']
+    assert len(ref['faces']) == 352
+    undecided = float((~r64['decided']).mean())
+    wrong = int(((r32['face'] != r64['face']) & r64['decided']).sum())
+    print(f'sphere {H}x{W}: {int((r64["face"] >= 0).sum())} covered pixels, undecided {undecided:.4%}, wrong float32 faces on decided pixels {wrong}')
+    assert undecided <= UNDECIDED_CAP and wrong == 0
+    cover = np.unique(r32['cover'])
+    print(f'sphere {H}x{W}: pixels are owned {cover.tolist()} times')
+    assert set(cover.tolist()) == {0, 2}
+    keep = (r32['face'] == r64['face']) & (r64['face'] >= 0) & r64['decided']
+    plain = R.plain32(ref['pos'], ref['faces'], r64['face'], H, W)
+    parity(f'sphere {H}x{W} uv', r32['uv'], plain['uv'], r64['uv'], keep=np.broadcast_to(keep[..., None], r32['uv'].shape).copy())
+    parity(f'sphere {H}x{W} zw', r32['zw'], plain['zw'], r64['zw'], keep=keep)
+    m = r64['face'] >= 0
+    print(f'sphere {H}x{W}: max |d u, v| {np.abs(r32["uv"][m] - r64["uv"][m]).max():.2e}, max |d zw| {np.abs(r32["zw"][m] - r64["zw"][m]).max():.2e}')
+
+
+def test_lattice_grid_is_owned_exactly_once():
+    pos, f = R.lattice_grid()
+    for dt in (np.float32, np.float64):
+        r = R.raster(pos, f, 16, 16, dt)
+        once, more = int((r['cover'] == 1).sum()), int((r['cover'] > 1).sum())
+        print(f'lattice {dt.__name__}: {once} pixels owned once, {more} more than once')
+        assert once == 64 and more == 0 and int((r['face'] >= 0).sum()) == 64
+    assert np.array_equal(R.raster(pos, f, 16, 16, np.float32)['face'], R.raster(pos, f, 16, 16, np.float64)['face'])
+
+
+def test_small_cases():
+    """one triangle in all vertex orders and windings covers the same pixels; w < 0, degenerate and stacked faces agree with float64"""
+    cases = R.triangle_cases()
+    masks = {}
+    for name, (pos, f) in cases.items():
+        r32, r64 = R.raster(pos, f, 32, 32, np.float32), R.raster(pos, f, 32, 32, np.float64)
+        wrong = int(((r32['face'] != r64['face']) & r64['decided']).sum())
+        print(f'{name}: {int((r32["face"] >= 0).sum())} pixels, {wrong} wrong on decided pixels, at most {int(r32["cover"].max())} faces on a pixel')
+        assert wrong == 0 and int((r32['face'] >= 0).sum()) > 0
+        masks[name] = r32['face'] >= 0
+    for name in ('tri120', 'tri201', 'tri021', 'tri210', 'tri102', 'degenerate'):
+        assert np.array_equal(masks[name], masks['tri012']), name
+    assert masks['w_negative'].sum() > masks['tri012'].sum() and int(R.raster(*cases['stacked'], 32, 32, np.float32)['cover'].max()) > 1
+    # the depth rule: reversing the face list changes the ids, not the picture
+    pos, f = cases['stacked']
+    a, b = R.raster(pos, f, 32, 32, np.float32), R.raster(pos, f[::-1].copy(), 32, 32, np.float32)
+    assert np.array_equal(a['zw'], b['zw']) and np.array_equal(a['uv'], b['uv'])
+    assert np.array_equal(np.where(a['face'] >= 0, len(f) - 1 - a['face'], -1), b['face'])
+
+
+def test_gradients():
+    H = W = 64
+    ref = R.sphere_reference(H, W, 2)
+    pos, faces, face, uv32 = ref['pos'], ref['faces'], ref['r32']['face'], ref['r32']['uv']
+    rng = np.random.default_rng(3)
+    V, A = pos.shape[1], 3
+    duv, dout = rng.standard_normal((2, H, W, 2)).astype(np.float32), rng.standard_normal((2, H, W, A)).astype(np.float32)
+    for kind, attr in (('shared', rng.standard_normal((V, A)).astype(np.float32)), ('per_view', rng.standard_normal((2, V, A)).astype(np.float32))):
+        a64 = R.grads_autograd(pos, faces, face, duv, attr, dout, torch.float64)
+        a32 = R.grads_autograd(pos, faces, face, duv, attr, dout, torch.float32)
+        c64 = R.grads_closed(pos, faces, a64['uv'], face, duv, attr, dout, np.float64)
+        c32 = R.grads_closed(pos, faces, uv32, face, duv, attr, dout, np.float32)
+        for k in ('dpos', 'dattr', 'duv_interp'):
+            rel = float(np.abs(c64[k] - a64[k]).max() / np.abs(a64[k]).max())
+            print(f'{kind} {k}: closed form against float64 autograd, relative {rel:.2e}')
+            assert rel <= 1e-9, (kind, k)
+            parity(f'{kind} {k} float32 closed form', c32[k], a32[k], a64[k])
+        seen = np.zeros(V, bool)
+        for b in range(2):
+            seen[np.unique(faces[face[b][face[b] >= 0]])] = True
+        assert (~seen).any() and not c32['dpos'][:, ~seen].any() and not c64['dattr'][..., ~seen, :].any()
+        assert not c64['dpos'][..., 2].any()
+
+
+@pytest.mark.parametrize('sanitize', (False, True), ids=('plain', 'sanitized'))
+def test_raster_rules_native(tmp_path, sanitize):
+    """tests/native/raster_rules_main.cpp: a stand-alone program (its own main) around csrc/ra_raster_rules.hpp, built plain and with
+    -fsanitize=address,undefined, run on the CPU"""
+    cxx = shutil.which('g++') or shutil.which('clang++') or shutil.which('c++')
+    assert cxx, 'no host C++ compiler'
+    exe = str(tmp_path / 'raster_rules_main')
+    flags = ['-std=c++17', '-O1', '-g', '-ffp-contract=off']
+    if sanitize:
+        flags += ['-fsanitize=address,undefined', '-fno-sanitize-recover=all']
+        flags += ['-static-libasan'] if os.path.basename(cxx).startswith('g++') else []      # gcc's spelling; clang links its runtime statically already
+    r = subprocess.run([cxx] + flags + ['-I', os.path.join(REPO, 'relightableavatar_amd', 'csrc'), os.path.join(REPO, 'tests', 'native', 'raster_rules_main.cpp'),
+                                        '-o', exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True)
+    print(r.stdout)
+    assert r.returncode == 0 and 'raster rules ok:' in r.stdout, r.stdout + r.stderr
+
+
+def test_python_layer_and_argument_errors():
+    import re
+    from relightableavatar_amd import _lib, engine, mesh_utils, raster_utils
+    hdr = open(os.path.join(REPO, 'include', 'relightableavatar.h')).read()
+    for sym in ('ra_rasterize', 'ra_rasterize_backward', 'ra_interpolate', 'ra_interpolate_backward', 'ra_raster_tile'):
+        assert sym in _lib.SYMBOLS and re.search(r'^int\s+' + sym + r'\s*\(', hdr, flags=re.M), sym
+    L = _lib.lib()
+    assert L.ra_abi_version() == 9
+    assert [L.ra_raster_tile(k) for k in range(4)] == [8, 256, 64, 0]
+    for fn in ('get_ndc_perspective_matrix', 'make_rotation_y', 'make_rotation', 'rasterize', 'interpolate', 'bilinear_interpolation', 'render_nvdiffrast'):
+        assert callable(getattr(raster_utils, fn)), fn
+    assert callable(mesh_utils.raster_maps) and all(hasattr(engine.Engine, k) for k in ('rasterize', 'interpolate', 'interpolate_backward', 'rasterize_backward'))
+    err = lambda: L.ra_last_error().decode()
+    p = C.c_void_p(16)          # never dereferenced: every call below fails on its arguments
+    # ra_rasterize(ctx, pos, B, V, faces, F, H, W, flags, uv, zw, face, stream)
+    for B, V, F, H, W in ((0, 4, 2, 8, 8), (1, 4, 2, 0, 8), (1, 4, 2, 8, 0), (1, 4, 1 << 24, 8, 8), (2, 4, 2, 1 << 15, 1 << 15), (1, 0, 2, 8, 8), (1, 4, -1, 8, 8)):
+        assert L.ra_rasterize(None, p, B, V, p, F, H, W, 0, p, p, p, None) != 0 and 'ra_rasterize: bad sizes' in err(), (B, V, F, H, W)
+    assert L.ra_rasterize(None, p, 1, 4, p, 2, 8, 8, 2, p, p, p, None) != 0 and 'ra_rasterize: unknown flag' in err()
+    assert L.ra_rasterize(None, p, 1, 4, p, 2, 8, 8, 0, p, p, p, None) != 0 and 'ra_rasterize: null argument' in err()
+    # ra_interpolate(ctx, attr, per_view, V, A, faces, F, uv, face, B, H, W, out, stream)
+    for A in (0, 65):
+        assert L.ra_interpolate(None, p, 0, 4, A, p, 2, p, p, 1, 8, 8, p, None) != 0 and 'ra_interpolate: bad sizes' in err(), A
+    assert L.ra_interpolate(None, p, 0, 4, 3, p, 2, p, p, 0, 8, 8, p, None) != 0 and 'ra_interpolate: bad sizes' in err()
+    assert L.ra_interpolate(None, p, 0, 4, 3, p, 2, p, p, 1, 8, 8, p, None) != 0 and 'ra_interpolate: null argument' in err()
+    # ra_interpolate_backward(ctx, topo, attr, per_view, V, A, uv, face, B, H, W, dout, dattr, duv, stream)
+    for A, B in ((0, 1), (65, 1), (3, 0)):
+        assert L.ra_interpolate_backward(None, p, p, 0, 4, A, p, p, B, 8, 8, p, p, p, None) != 0 and 'ra_interpolate_backward: bad sizes' in err(), (A, B)
+    assert L.ra_interpolate_backward(None, p, p, 0, 4, 3, p, p, 1, 8, 8, p, p, p, None) != 0 and 'ra_interpolate_backward: null argument' in err()
+    # ra_rasterize_backward(ctx, topo, pos, B, V, H, W, uv, face, duv, dpos, stream)
+    assert L.ra_rasterize_backward(None, p, p, 1, 4, 0, 8, p, p, p, p, None) != 0 and 'ra_rasterize_backward: bad sizes' in err()
+    assert L.ra_rasterize_backward(None, p, p, 1, 4, 8, 8, p, p, p, p, None) != 0 and 'ra_rasterize_backward: null argument' in err()
+    with pytest.raises(NotImplementedError):
+        raster_utils.render_nvdiffrast(torch.zeros(3, 3), torch.zeros(1, 3, dtype=torch.int32), torch.zeros(3, 1), uv=torch.zeros(3, 2), img=torch.zeros(1, 2, 2, 3))
+    with pytest.raises(NotImplementedError):
+        raster_utils.interpolate(torch.zeros(3, 1), torch.zeros(1, 2, 2, 4), torch.zeros(1, 3, dtype=torch.int32), rast_db=torch.zeros(1))
+    with pytest.raises(ValueError):
+        raster_utils.rasterize(torch.zeros(3, 4), torch.zeros(1, 3, dtype=torch.int32), 4, 4)
