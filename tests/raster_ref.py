@@ -7,6 +7,10 @@
   plain32(...)                           the float32 baseline of the 10 x rule: per-face adjoint coefficients, no named order
   interp(...), grads_closed(...)         interpolation and the closed-form gradients the kernels use, in either precision
   grads_autograd(...)                    torch autograd through the float64 (or float32) barycentrics with the face map held fixed
+  grads_kernel_order(...)                the backward kernels' float32 operations in the kernels' order (lane sums, xor tree, half-edge
+                                         order): what the three gradients must equal bit for bit
+  run_length_cases(), open_case(),       the cases of the backward passes: one face owning 1 .. 193 pixels, w < 0, H != W, partial tiles,
+  backward_case(name), ...               two and three views, an empty image, boundaries and unreferenced vertices
 The clip-space positions are float32 inputs; every restatement starts from the same float32 values.
 """
 import functools
@@ -301,14 +305,222 @@ def grads_autograd(pos, faces, face_map, duv, attr, dout, dtype):
     return dict(dpos=dpos.numpy(), dattr=dattr.numpy(), duv_interp=duv_i.numpy(), uv=uv.detach().numpy())
 
 
+def _freeze(out):
+    for a in out.values():
+        if isinstance(a, dict):
+            _freeze(a)
+        elif isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return out
+
+
 @functools.lru_cache(None)
 def sphere_reference(H, W, views=1):
-    """the shared, read-only references of the sphere at one size: pos, faces, the float32 and float64 restatements"""
+    """the shared, read-only references of the sphere at one size and any number of views (view k is rotated by 0.6 + 0.9 k): pos, faces,
+    the float32 and float64 restatements"""
     poses = [sphere_case(H, W, 0.6 + 0.9 * k) for k in range(views)]
     pos, faces = np.stack([p for p, _ in poses]), poses[0][1]
-    out = dict(pos=pos, faces=faces, r32=raster(pos, faces, H, W, np.float32), r64=raster(pos, faces, H, W, np.float64))
-    for d in (out['r32'], out['r64']):
-        for a in d.values():
-            a.setflags(write=False)
-    pos.setflags(write=False)
+    return _freeze(dict(pos=pos, faces=faces, r32=raster(pos, faces, H, W, np.float32), r64=raster(pos, faces, H, W, np.float64)))
+
+
+# ---- the cases of the backward passes: runs of a face's pixels longer than one wave ------------------------------------------------------
+RUN_LENGTHS = (1, 2, 63, 64, 65, 127, 128, 129, 193)
+
+
+def scale_ndc(pos, s):
+    """(V,4) float32 -> the vertices scaled by s about their centroid in NDC (x / w, y / w); z and w kept"""
+    p = pos.astype(np.float64)
+    ndc = p[:, :2] / p[:, 3:4]
+    c = ndc.mean(0)
+    out = p.copy()
+    out[:, :2] = (c + s * (ndc - c)) * p[:, 3:4]
+    return out.astype(np.float32)
+
+
+@functools.lru_cache(None)
+def run_length_cases():
+    """n -> (scale, pos (3,4) float32, faces): triangle_cases()['tri012'] scaled so that raster(..., np.float32) covers exactly n pixels of
+    32 x 32, for every n of RUN_LENGTHS: one pixel short of a wave, a full wave, one pixel into the lane loop's second trip, likewise
+    around 128, and a run that ends inside the fourth trip.  The scale is the first of a fixed sweep (2301 steps over [0.05, 1.2]) that
+    gives the count, and the count is asserted: a change to the rule shows up here, not as a silent loss of coverage."""
+    tri, f = triangle_cases()['tri012']
+    count = lambda pos: int((raster(pos, f, 32, 32, np.float32)['face'] >= 0).sum())
+    found = {}
+    for s in np.linspace(0.05, 1.2, 2301):
+        pos = scale_ndc(tri, s)
+        n = count(pos)
+        if n in RUN_LENGTHS and n not in found:
+            found[n] = (float(s), pos, f)
+            if len(found) == len(RUN_LENGTHS):
+                break
+    missing = [n for n in RUN_LENGTHS if n not in found]
+    assert not missing, f'the sweep found no scale that covers {missing} pixels'
+    for n, (s, pos, _) in found.items():
+        assert count(pos) == n, (n, s)
+        pos.setflags(write=False)
+    return {n: found[n] for n in RUN_LENGTHS}
+
+
+def open_case(H=37, W=53):
+    """(pos (V + 3, 4) float32, faces): every second face of the sphere, so that every remaining face has a boundary edge, and three
+    vertices no face references (one of them at w < 0)"""
+    pos, f = sphere_case(H, W)
+    extra = np.array([[0.1, 0.2, 0.0, 1.0], [-0.45, 0.15, 0.3, 1.5], [0.2, -0.1, 0.1, -1.0]], np.float32)
+    return np.concatenate([pos, extra]), f[::2].copy()
+
+
+@functools.lru_cache(None)
+def backward_case_list():
+    """name -> (pos (B,V,4) float32, faces, H, W): what the backward passes are pinned on (sizes are H x W)"""
+    tri = triangle_cases()
+    out = {f'run_{n}': (pos[None], f, 32, 32) for n, (_, pos, f) in run_length_cases().items()}
+    out['w_negative_130x70'] = (tri['w_negative'][0][None], tri['w_negative'][1], 130, 70)
+    out['w_negative_32x32'] = (tri['w_negative'][0][None], tri['w_negative'][1], 32, 32)
+    out['tri012_37x53'] = (tri['tri012'][0][None], tri['tri012'][1], 37, 53)
+    for name, (H, W, views) in (('sphere2_200x136', (200, 136, 2)), ('sphere2_136x200', (136, 200, 2)), ('sphere3_37x53', (37, 53, 3)), ('sphere2_9x7', (9, 7, 2)),
+                                ('sphere_1x1', (1, 1, 1))):
+        ref = sphere_reference(H, W, views)
+        out[name] = (ref['pos'], ref['faces'], H, W)
+    out['stacked_32x32'] = (tri['stacked'][0][None], tri['stacked'][1], 32, 32)
+    pos, f = open_case()
+    out['open_37x53'] = (pos[None], f, 37, 53)
     return out
+
+
+BACKWARD_CASES = ('run_1', 'run_2', 'run_63', 'run_64', 'run_65', 'run_127', 'run_128', 'run_129', 'run_193', 'w_negative_130x70', 'w_negative_32x32',
+                  'tri012_37x53', 'sphere2_200x136', 'sphere2_136x200', 'sphere3_37x53', 'sphere2_9x7', 'sphere_1x1', 'stacked_32x32', 'open_37x53')
+WIDE_CASES = ('run_65', 'w_negative_130x70')         # these also run with 1 and 64 channels
+BACKWARD_PARAMS = tuple((name, A) for name in BACKWARD_CASES for A in ((1, 3, 64) if name in WIDE_CASES else (3,)))
+
+
+@functools.lru_cache(None)
+def backward_case(name):
+    """the shared, read-only references of one case: pos, faces, H, W, the float32 and float64 restatements, `runs` (the number of pixels of
+    every (view, face) that owns one, from the float32 face map), a seeded duv"""
+    pos, faces, H, W = backward_case_list()[name]
+    if name.startswith('sphere'):
+        ref = sphere_reference(H, W, pos.shape[0])
+        r32, r64 = ref['r32'], ref['r64']
+    else:
+        r32, r64 = raster(pos, faces, H, W, np.float32), raster(pos, faces, H, W, np.float64)
+    runs = np.concatenate([np.bincount(m[m >= 0], minlength=len(faces)) for m in r32['face'].reshape(pos.shape[0], -1)])
+    rng = np.random.default_rng(_seed(name))
+    return _freeze(dict(pos=pos, faces=faces, H=H, W=W, r32=r32, r64=r64, runs=runs[runs > 0],
+                        duv=rng.standard_normal(r32['uv'].shape).astype(np.float32)))
+
+
+def _seed(name):
+    return sum((i + 1) * ord(ch) for i, ch in enumerate(name)) % (2 ** 31)
+
+
+@functools.lru_cache(None)
+def backward_reference(name, A, kind):
+    """one case with A channels of `shared` (V,A) or `per_view` (B,V,A) attributes: attr and dout (seeded), `kernel` =
+    grads_kernel_order on the float32 forward, `a32` / `a64` = grads_autograd with the float32 face map held fixed.  Read-only."""
+    import torch
+    c = backward_case(name)
+    B, V = c['pos'].shape[:2]
+    rng = np.random.default_rng(_seed(f'{name} {A} {kind}'))
+    attr = rng.standard_normal((V, A) if kind == 'shared' else (B, V, A)).astype(np.float32)
+    dout = rng.standard_normal((B, c['H'], c['W'], A)).astype(np.float32)
+    face = c['r32']['face']
+    return _freeze(dict(attr=attr, dout=dout, kernel=grads_kernel_order(c['pos'], c['faces'], c['r32']['uv'], face, c['duv'], attr, dout),
+                        a32=grads_autograd(c['pos'], c['faces'], face, c['duv'], attr, dout, torch.float32),
+                        a64=grads_autograd(c['pos'], c['faces'], face, c['duv'], attr, dout, torch.float64)))
+
+
+# ---- the backward kernels' float32 operations in the kernels' order ------------------------------------------------------------------------
+def _wave_sum(terms):
+    """terms (n, ...) float32 of a run's pixels, ascending -> what lane 0 holds: lane l adds terms l, l + 64, ... in that order from 0,
+    then the 64 lane sums meet in the tree x[l] + x[l ^ w], w = 32, 16, .., 1"""
+    x = np.zeros((64,) + terms.shape[1:], np.float32)
+    for i in range(0, terms.shape[0], 64):
+        m = min(64, terms.shape[0] - i)
+        x[:m] = x[:m] + terms[i:i + m]
+    lanes = np.arange(64)
+    for w in (32, 16, 8, 4, 2, 1):
+        x = x + x[lanes ^ w]
+    return x[0]
+
+
+def _cross32(a, b):
+    """raster_cross: every product and every difference rounded once"""
+    return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]], np.float32)
+
+
+def grads_kernel_order(pos, faces, uv32, face_map, duv, attr, dout):
+    """interp_duv_kernel, interp_face_kernel + interp_vertex_kernel and raster_face_bwd_kernel + raster_vertex_bwd_kernel of ra_raster.hip
+    restated: their float32 operations in their order, one numpy float32 operation per rounding (the file and ra_raster_rules.hpp turn
+    contraction off and name every operation).  What the device must equal bit for bit, given the forward's uv32 and face_map:
+    dict(dpos (B,V,4), dattr shaped like attr, duv_interp (B,H,W,2))."""
+    f32 = np.float32
+    pos = (pos[None] if pos.ndim == 2 else pos).astype(f32)
+    B, V = pos.shape[:2]
+    H, W = face_map.shape[1:]
+    F = len(faces)
+    shared = attr.ndim == 2
+    a = np.broadcast_to(attr, (B,) + attr.shape[-2:]).astype(f32)
+    A = a.shape[-1]
+    uv, duv, dout = uv32.astype(f32).reshape(B, H * W, 2), duv.astype(f32).reshape(B, H * W, 2), dout.astype(f32).reshape(B, H * W, A)
+    one = f32(1)
+    g_attr, g_pos = np.zeros((B, 3 * F, A), f32), np.zeros((B, 3 * F, 3), f32)       # the corner scratch, indexed by the half-edge 3 f + corner
+    duv_i = np.zeros((B, H * W, 2), f32)
+    with np.errstate(all='ignore'):
+        for b in range(B):
+            flat = face_map[b].reshape(-1)
+            # interp_duv_kernel: one pixel each, the channels ascending
+            q = np.flatnonzero(flat >= 0)
+            corner = a[b][faces[flat[q]]]           # (n,3,A)
+            du, dv = np.zeros(len(q), f32), np.zeros(len(q), f32)
+            for ch in range(A):
+                d = dout[b, q, ch]
+                e0, e1 = corner[:, 0, ch] - corner[:, 2, ch], corner[:, 1, ch] - corner[:, 2, ch]
+                du = du + d * e0
+                dv = dv + d * e1
+            duv_i[b, q, 0], duv_i[b, q, 1] = du, dv
+            for f in np.unique(flat[q]):
+                q = np.flatnonzero(flat == f)           # the run: the face's pixels, ascending
+                u, v = uv[b, q, 0], uv[b, q, 1]
+                # interp_face_kernel
+                b2 = (one - u) - v
+                d = dout[b, q]
+                g_attr[b, 3 * f], g_attr[b, 3 * f + 1], g_attr[b, 3 * f + 2] = _wave_sum(u[:, None] * d), _wave_sum(v[:, None] * d), _wave_sum(b2[:, None] * d)
+                # raster_face_bwd_kernel
+                idx = faces[f]
+                c, neg = setup([pos[b, i] for i in idx], idx, H, W, f32, box=False)[:2]
+                iy = q // W
+                ix = q - iy * W
+                px, py = centre(ix, W, f32), centre(iy, H, f32)
+                E = [(c[k, 0] * px + c[k, 1] * py) + c[k, 2] for k in range(3)]
+                e = [-E[k] if neg[k] else E[k] for k in range(3)]
+                S = (e[0] + e[1]) + e[2]
+                gu, gv = duv[b, q, 0], duv[b, q, 1]
+                uu, vv = gu * u, gv * v
+                n0, n1, n2 = (gu - uu) - vv, (gv - vv) - uu, uu + vv
+                g = [n0 / S, n1 / S, -n2 / S]
+                G = _wave_sum(np.stack([t for k in range(3) for t in (g[k] * px, g[k] * py, g[k])], 1))
+                G = [G[0:3], G[3:6], G[6:9]]
+                Vx = [pos[b, i][[0, 1, 3]] for i in idx]
+                g_pos[b, 3 * f] = _cross32(G[1], Vx[2]) + _cross32(Vx[1], G[2])
+                g_pos[b, 3 * f + 1] = _cross32(G[2], Vx[0]) + _cross32(Vx[2], G[0])
+                g_pos[b, 3 * f + 2] = _cross32(G[0], Vx[1]) + _cross32(Vx[0], G[1])
+        # the vertex passes: a vertex's corners in ascending half-edge order, each view's sum first, then the views ascending
+        corners = faces.reshape(-1)
+        order = np.argsort(corners, kind='stable')
+        start = np.searchsorted(corners[order], np.arange(V + 1))
+        dpos, per_view = np.zeros((B, V, 4), f32), np.zeros((B, V, A), f32)
+        for b in range(B):
+            for v in range(V):
+                sp, sa = np.zeros(3, f32), np.zeros(A, f32)
+                for h in order[start[v]:start[v + 1]]:
+                    sp = sp + g_pos[b, h]
+                    sa = sa + g_attr[b, h]
+                dpos[b, v, [0, 1, 3]] = sp
+                per_view[b, v] = sa
+        if shared:
+            dattr = np.zeros((V, A), f32)
+            for b in range(B):
+                dattr = dattr + per_view[b]
+        else:
+            dattr = np.zeros((B, V, A), f32) + per_view
+    return dict(dpos=dpos, dattr=dattr, duv_interp=duv_i.reshape(B, H, W, 2))

@@ -1,7 +1,8 @@
 """ra_rasterize, ra_interpolate and their backward passes on the device.  Run with `-m gpu` on an MI355X.
 
 Exactness is bit equality: ra_rasterize equals the kernel-order numpy restatement (tests/raster_ref.py), the binned call equals
-RA_RASTER_BRUTE, a repeat gives the same bits, a view of a batch equals the call of that view alone.  Arithmetic outputs are held to the
+RA_RASTER_BRUTE, a repeat gives the same bits, a view of a batch equals the call of that view alone, and the three gradients equal
+raster_ref.grads_kernel_order on faces that own from 1 to 4 363 pixels.  Arithmetic outputs are held to the
 project's 10 x float32 rule (frame_stage_ref.parity) against float64; the float32 reference is raster_ref.plain32 / torch autograd in
 float32, the float64 one raster_ref's exhaustive restatement / torch autograd in float64 with the face map held fixed.  Every test
 prints its figures before it asserts."""
@@ -363,3 +364,252 @@ def test_foreign_topology_is_refused(eng):
     with pytest.raises(_lib.RaError, match='bad sizes'):
         eng.interpolate_backward(topo, a, rast, d)
     topo.close()
+
+
+# ---- the backward passes on faces that own more than one wave of pixels (tests/raster_ref.py: backward_case_list) -------------------------
+def same_bits(tag, got, ref):
+    """prints the verdict and returns it: the asserts come after every figure of the test is printed"""
+    x, y = bits(got), bits(torch.as_tensor(np.ascontiguousarray(ref)))
+    same = x.shape == y.shape and bool(torch.equal(x, y))
+    print(f'{tag}: bit-equal {same} ({x.numel()} values, {int((x != y).sum()) if x.shape == y.shape else -1} differ)')
+    return same
+
+
+def forward_of(eng, name):
+    """the device's forward of a case, asserted equal to the restatement: the backward references start from the restatement's uv and face"""
+    c = R.backward_case(name)
+    rast = eng.rasterize(T(c['pos']), T(c['faces']), c['H'], c['W'])
+    same_maps(f'{name} forward vs restatement', rast, {k: torch.tensor(c['r32'][k]) for k in ('uv', 'zw', 'face')})
+    return c, rast
+
+
+def seen_vertices(c, b):
+    face = c['r32']['face'][b]
+    seen = np.zeros(c['pos'].shape[1], bool)
+    seen[np.unique(c['faces'][face[face >= 0]])] = True
+    return seen
+
+
+@pytest.mark.parametrize('name,A', R.BACKWARD_PARAMS)
+@pytest.mark.parametrize('kind', ['shared', 'per_view'])
+def test_interpolate_backward_runs(eng, name, A, kind):
+    """d attr and d uv equal the kernel-order restatement bit for bit, hold the 10 x rule against float32 and float64 autograd, repeat
+    with the same bits, and are exactly 0 where nothing is seen"""
+    c, rast = forward_of(eng, name)
+    g = R.backward_reference(name, A, kind)
+    topo = eng.topology(T(c['faces']), c['pos'].shape[1])
+    got = eng.interpolate_backward(topo, T(g['attr']), rast, T(g['dout']))
+    again = eng.interpolate_backward(topo, T(g['attr']), rast, T(g['dout']))
+    topo.close()
+    runs = c['runs']
+    print(f'{name} A={A} {kind}: {len(runs)} runs, largest {int(runs.max()) if len(runs) else 0}, {int((runs > 64).sum())} above 64')
+    ok = [same_bits(f'{name} A={A} {kind} d attr vs kernel order', got.dattr, g['kernel']['dattr']),
+          same_bits(f'{name} A={A} {kind} d uv vs kernel order', got.duv, g['kernel']['duv_interp']),
+          same_bits(f'{name} A={A} {kind} d attr repeat', again.dattr, got.dattr.cpu().numpy()),
+          same_bits(f'{name} A={A} {kind} d uv repeat', again.duv, got.duv.cpu().numpy())]
+    parity(f'{name} A={A} {kind} d attr', got.dattr.cpu(), g['a32']['dattr'], g['a64']['dattr'])
+    parity(f'{name} A={A} {kind} d uv', got.duv.cpu(), g['a32']['duv_interp'], g['a64']['duv_interp'])
+    assert all(ok), ok
+    dattr = got.dattr.cpu().numpy()
+    seen = np.stack([seen_vertices(c, b) for b in range(c['pos'].shape[0])])
+    unseen = ~seen.any(0) if kind == 'shared' else ~seen
+    assert not dattr[unseen].any() and not got.duv.cpu().numpy()[c['r32']['face'] < 0].any()
+    if name == 'sphere_1x1':
+        assert not dattr.any() and not got.duv.cpu().numpy().any()
+
+
+@pytest.mark.parametrize('name', R.BACKWARD_CASES)
+def test_rasterize_backward_runs(eng, name):
+    """d pos equals the kernel-order restatement bit for bit, holds the 10 x rule against float32 and float64 autograd, repeats with the
+    same bits, carries nothing in z and is exactly 0 at vertices no pixel sees or no face references"""
+    c, rast = forward_of(eng, name)
+    g = R.backward_reference(name, 3, 'shared')
+    pos = T(c['pos'])
+    topo = eng.topology(T(c['faces']), pos.shape[1])
+    got = eng.rasterize_backward(topo, pos, rast, T(c['duv']))
+    again = eng.rasterize_backward(topo, pos, rast, T(c['duv']))
+    topo.close()
+    runs = c['runs']
+    print(f'{name}: {len(runs)} runs, largest {int(runs.max()) if len(runs) else 0}, {int((runs > 64).sum())} above 64')
+    ok = [same_bits(f'{name} d pos vs kernel order', got, g['kernel']['dpos']), same_bits(f'{name} d pos repeat', again, got.cpu().numpy())]
+    parity(f'{name} d pos', got.cpu(), g['a32']['dpos'], g['a64']['dpos'])
+    assert all(ok), ok
+    d = got.cpu().numpy()
+    assert not d[..., 2].any()
+    for b in range(d.shape[0]):
+        seen = seen_vertices(c, b)
+        print(f'{name} view {b}: {int(seen.sum())} of {len(seen)} vertices seen')
+        assert not d[b, ~seen].any() and (not seen.any() or d[b, seen].any())
+    if name == 'sphere_1x1':
+        assert not d.any()
+    if name == 'open_37x53':
+        assert not d[:, -3:].any()
+
+
+def test_three_views_are_independent(eng):
+    """B = 3: row b of d pos and of per-view d attr equals the B = 1 call of that view; d uv likewise"""
+    name = 'sphere3_37x53'
+    c, rast = forward_of(eng, name)
+    g = R.backward_reference(name, 3, 'per_view')
+    pos, f = T(c['pos']), T(c['faces'])
+    topo = eng.topology(f, pos.shape[1])
+    attr, dout, duv = T(g['attr']), T(g['dout']), T(c['duv'])
+    dpos, di = eng.rasterize_backward(topo, pos, rast, duv), eng.interpolate_backward(topo, attr, rast, dout)
+    ok = []
+    for b in range(3):
+        v = slice(b, b + 1)
+        one = eng.rasterize(pos[v], f, c['H'], c['W'])
+        same_maps(f'{name} view {b} alone', rast, one, v)
+        alone = eng.interpolate_backward(topo, attr[v], one, dout[v])
+        ok += [same_bits(f'{name} d pos view {b} alone', eng.rasterize_backward(topo, pos[v], one, duv[v]), dpos[v].cpu().numpy()),
+               same_bits(f'{name} d attr view {b} alone', alone.dattr, di.dattr[v].cpu().numpy()),
+               same_bits(f'{name} d uv view {b} alone', alone.duv, di.duv[v].cpu().numpy())]
+    topo.close()
+    assert all(ok), ok
+    assert not torch.equal(dpos[0], dpos[1]) and not torch.equal(dpos[1], dpos[2])
+
+
+@pytest.mark.parametrize('name', ['run_65', 'sphere2_136x200', 'sphere_1x1'])
+def test_want_subsets(eng, name):
+    """interpolate_backward(want=('dattr',)) and (want=('duv',)) return the bits of the matching half of the full call"""
+    c, rast = forward_of(eng, name)
+    ok = []
+    topo = eng.topology(T(c['faces']), c['pos'].shape[1])
+    for kind in ('shared', 'per_view'):
+        g = R.backward_reference(name, 3, kind)
+        attr, dout = T(g['attr']), T(g['dout'])
+        full = eng.interpolate_backward(topo, attr, rast, dout)
+        only_a, only_uv = eng.interpolate_backward(topo, attr, rast, dout, want=('dattr',)), eng.interpolate_backward(topo, attr, rast, dout, want=('duv',))
+        assert sorted(only_a) == ['dattr'] and sorted(only_uv) == ['duv']
+        ok += [same_bits(f'{name} {kind} want dattr', only_a.dattr, full.dattr.cpu().numpy()), same_bits(f'{name} {kind} want duv', only_uv.duv, full.duv.cpu().numpy()),
+               same_bits(f'{name} {kind} full d attr vs kernel order', full.dattr, g['kernel']['dattr']),
+               same_bits(f'{name} {kind} full d uv vs kernel order', full.duv, g['kernel']['duv_interp'])]
+    topo.close()
+    assert all(ok), ok
+
+
+@pytest.mark.parametrize('name', ['w_negative_130x70', 'sphere2_200x136', 'sphere2_136x200', 'sphere3_37x53', 'open_37x53'])
+def test_rasterize_bits_at_the_new_shapes(eng, name):
+    """the forward at the shapes of the backward cases: partial tiles on both axes, H != W, three views, boundaries — equal to the
+    restatement, to RA_RASTER_BRUTE and to a repeat, bit for bit"""
+    c, got = forward_of(eng, name)
+    pos, f = T(c['pos']), T(c['faces'])
+    print(f'{name}: {int((got.face >= 0).sum())} covered pixels of {got.face.numel()}')
+    same_maps(f'{name} brute', got, eng.rasterize(pos, f, c['H'], c['W'], brute=True))
+    same_maps(f'{name} repeat', got, eng.rasterize(pos, f, c['H'], c['W']))
+    empty = (got.face < 0).cpu()
+    assert bool((got.uv.cpu()[empty] == 0).all()) and bool((got.zw.cpu()[empty] == 0).all())
+    r64 = c['r64']
+    wrong = int(((got.face.cpu().numpy() != r64['face']) & r64['decided']).sum())
+    print(f'{name}: undecided {float((~r64["decided"]).mean()):.4%}, wrong faces on decided pixels {wrong}')
+    assert wrong == 0
+
+
+def test_scratch_reuse(eng):
+    """the ctx's grow-only scratch (raster_keys, raster_pix_sorted, raster_sort_tmp, raster_g_face): a small call after a large one
+    ignores the stale tail.  One ctx, in order: the 9 x 7 sphere, the w < 0 triangle at 130 x 70 (4 363 pixels on one face, 64 channels),
+    the 9 x 7 sphere again — forward and both backwards each time —, then ra_interpolate_backward with 64 channels and ra_rasterize_backward
+    on the 9 x 7 sphere, which share raster_g_face (B F 3 A floats, then B F 9)"""
+    def run(name, A):
+        c = R.backward_case(name)
+        g = R.backward_reference(name, A, 'shared')
+        pos, f = T(c['pos']), T(c['faces'])
+        rast = eng.rasterize(pos, f, c['H'], c['W'])
+        topo = eng.topology(f, pos.shape[1])
+        di = eng.interpolate_backward(topo, T(g['attr']), rast, T(g['dout']))
+        dpos = eng.rasterize_backward(topo, pos, rast, T(c['duv']))
+        topo.close()
+        out = dict(uv=rast.uv.cpu().numpy(), zw=rast.zw.cpu().numpy(), face=rast.face.cpu().numpy(), dattr=di.dattr.cpu().numpy(), duv_interp=di.duv.cpu().numpy(),
+                   dpos=dpos.cpu().numpy())
+        ref = dict(c['r32'], **g['kernel'])
+        return out, [same_bits(f'scratch reuse, {name} A={A}: {k} vs restatement', out[k], ref[k]) for k in out]
+    first, ok1 = run('sphere2_9x7', 3)
+    _, ok2 = run('w_negative_130x70', 64)
+    second, ok3 = run('sphere2_9x7', 3)
+    ok4 = [same_bits(f'scratch reuse, second 9 x 7 call vs first: {k}', second[k], first[k]) for k in first]
+    wide, ok5 = run('sphere2_9x7', 64)          # interpolate_backward with 64 channels, then rasterize_backward in the same scratch
+    ok5 += [same_bits('scratch reuse, d pos after the 64-channel call vs first', wide['dpos'], first['dpos'])]
+    assert all(ok1) and all(ok2) and all(ok3) and all(ok4) and all(ok5), (ok1, ok2, ok3, ok4, ok5)
+
+
+# ---- render_nvdiffrast and raster_maps by value ---------------------------------------------------------------------------------------------
+def resize64(x, H, W, dtype=torch.float64):
+    """(B,h,w,C) numpy -> (B,H,W,C): bilinear, align_corners=False, in the given precision on the CPU"""
+    t = torch.from_numpy(np.ascontiguousarray(x)).to(dtype).permute(0, 3, 1, 2)
+    return torch.nn.functional.interpolate(t, [H, W], mode='bilinear', align_corners=False).permute(0, 2, 3, 1).numpy()
+
+
+def render_restated(clip, faces, attrs, H, W, R_S):
+    """render_nvdiffrast's attribute path restated from the float32 clip positions: raster in float64 at R_S times the size, interp,
+    bilinear resize in float64; the float32 baseline is the same steps on plain32's barycentrics.  keep: output pixels whose source
+    pixels are all decided (there the float32 face is the float64 face: asserted)."""
+    h, w = H * R_S, W * R_S
+    r64, r32 = R.raster(clip, faces, h, w, np.float64), R.raster(clip, faces, h, w, np.float32)
+    assert int(((r32['face'] != r64['face']) & r64['decided']).sum()) == 0
+    face = r64['face']
+    img64 = resize64(R.interp(attrs, faces, r64['uv'], face, np.float64), H, W)
+    img32 = resize64(R.interp(attrs, faces, R.plain32(clip, faces, face, h, w)['uv'], face, np.float32), H, W, torch.float32)
+    msk64 = resize64((face >= 0)[..., None], H, W)[..., 0]
+    keep = resize64(r64['decided'][..., None], H, W)[..., 0] == 1
+    return dict(img64=img64, img32=img32, msk64=msk64, keep=keep)
+
+
+@pytest.mark.parametrize('size', [(32, 32), (37, 53)])
+@pytest.mark.parametrize('R_S', [1, 2])
+def test_render_nvdiffrast_by_value(eng, size, R_S):
+    """render_nvdiffrast's image under the 10 x rule and its mask exactly, on the output pixels whose source pixels are all decided"""
+    H, W = size
+    verts, faces = R.uv_sphere()
+    cams = [R.camera(H, W, angle) for angle in (0.6, 1.5)]
+    v, f = T(verts.astype(np.float32)), T(faces)
+    Rt, Tt = T(np.stack([c[1] for c in cams]).astype(np.float32)), T(np.stack([c[2] for c in cams]).astype(np.float32))[..., None]
+    P = raster_utils.get_ndc_perspective_matrix(T(np.stack([c[0] for c in cams]).astype(np.float32)), H, W)
+    attrs = np.random.default_rng(7).standard_normal((len(verts), 5)).astype(np.float32)
+    img, msk = raster_utils.render_nvdiffrast(v, f, T(attrs), H=H, W=W, R=Rt, T=Tt, K=P, R_S=R_S, engine=eng)
+    # step 1, the same float32 clip positions: render_nvdiffrast's own expressions on the same device tensors
+    vv = v[None].expand(2, -1, -1).contiguous() @ Rt.mT + Tt.mT
+    clip = (torch.cat([vv, vv.new_ones((*vv.shape[:-1], 1))], dim=-1) @ P.mT).cpu().numpy()
+    ref = render_restated(clip, faces, attrs, H, W, R_S)
+    covered = ref['msk64'] > 0
+    left_out = float((covered & ~ref['keep']).sum() / covered.sum())
+    mask_same = bool(np.array_equal(msk.cpu().numpy()[ref['keep']], ref['msk64'][ref['keep']].astype(np.float32)))
+    soft = int(((ref['msk64'] > 0) & (ref['msk64'] < 1)).sum())
+    print(f'render_nvdiffrast {H}x{W} R_S={R_S}: {int(covered.sum())} covered output pixels, {left_out:.4%} of them left out, {soft} soft mask pixels, mask exact {mask_same}')
+    assert img.shape == (2, H, W, 5) and msk.shape == (2, H, W) and img.dtype == msk.dtype == torch.float32
+    keep = np.broadcast_to(ref['keep'][..., None], img.shape).copy()
+    parity(f'render_nvdiffrast {H}x{W} R_S={R_S} image', img.cpu(), ref['img32'], ref['img64'], keep=keep)
+    assert left_out <= 0.01 and mask_same and (soft > 0) == (R_S > 1)
+    assert not img.cpu().numpy()[(ref['msk64'] == 0) & ref['keep']].any()
+
+
+@pytest.mark.parametrize('size', [(32, 32), (37, 53)])
+def test_raster_maps_by_value(eng, size):
+    """raster_maps: the face is the float64 face on decided pixels; depth and normal under the 10 x rule against the float64 restatement"""
+    H, W = size
+    verts, faces = R.uv_sphere()
+    K, Rm, Tv = R.camera(H, W)
+    v32 = verts.astype(np.float32)
+    v, f = T(v32), T(faces)
+    maps = mesh_utils.raster_maps(v, f, H, W, K, Rm, Tv, engine=eng)
+    # the same float32 camera-space and clip positions: raster_maps' own expressions on the same device tensors
+    Kt, Rt, Tt = (torch.as_tensor(x).to(device=DEV, dtype=torch.float32) for x in (K, Rm, Tv))
+    cam = v @ Rt.mT + Tt.reshape(1, 3)
+    clip = (torch.cat([cam, torch.ones_like(cam[:, :1])], dim=-1) @ raster_utils.get_ndc_perspective_matrix(Kt, H, W).mT).cpu().numpy()
+    z = cam[:, 2:3].cpu().numpy()
+    r64 = R.raster(clip, faces, H, W, np.float64)
+    face64, decided = r64['face'][0], r64['decided'][0]
+    got_face = maps.face.cpu().numpy()
+    wrong = int(((got_face != face64) & decided).sum())
+    keep = decided & (face64 >= 0) & (got_face == face64)
+    covered = face64 >= 0
+    left_out = float((covered & ~keep).sum() / covered.sum())
+    print(f'raster_maps {H}x{W}: {int(covered.sum())} covered pixels, {wrong} wrong faces on decided pixels, {left_out:.4%} left out')
+    depth64 = R.interp(z, faces, r64['uv'], r64['face'], np.float64)[0]
+    depth32 = R.interp(z, faces, R.plain32(clip, faces, r64['face'], H, W)['uv'], r64['face'], np.float32)[0]
+    normal = lambda dt: (lambda t: np.cross(t[..., 1, :] - t[..., 0, :], t[..., 2, :] - t[..., 0, :]))(v32.astype(dt)[faces[np.maximum(face64, 0)]])
+    unit = lambda n: np.where(covered[..., None], n / np.linalg.norm(n, axis=-1, keepdims=True), 0).astype(n.dtype)
+    parity(f'raster_maps {H}x{W} depth', maps.depth_map.cpu(), depth32, depth64, keep=keep[..., None])
+    parity(f'raster_maps {H}x{W} normal', maps.norm_map.cpu(), unit(normal(np.float32)), unit(normal(np.float64)), keep=np.broadcast_to(keep[..., None], (H, W, 3)).copy())
+    assert wrong == 0 and left_out <= 0.01
+    assert np.array_equal(maps.acc_map.cpu().numpy()[..., 0] > 0, got_face >= 0)
+    assert not maps.depth_map.cpu().numpy()[got_face < 0].any() and not maps.norm_map.cpu().numpy()[got_face < 0].any()

@@ -4,6 +4,8 @@
        what ra_rasterize must equal bit for bit on the device — returns the float64 face on every decided pixel, keeps u, v, zw under
        the 10 x float32 rule against a plain float32 restatement, and owns pixels exactly (closed sphere: 0 or 2; lattice grid: 64 once);
     3. the closed-form gradients the kernels use match torch autograd in float64 to 1e-9, and in float32 stay under the 10 x rule;
+       the cases of the backward passes (runs of 1 .. 4 363 pixels per face) are classified, their histograms of pixels per face hold what
+       they were built for, and the kernel-order restatement of the backward stays under the 10 x rule on each;
     4. tests/native/raster_rules_main.cpp: the complementarity lemma and the depth rule's order independence, plain and sanitized;
     5. argument errors of the four entry points are raised before any launch (no ctx is needed to name them).
 Every test prints its figures before it asserts."""
@@ -116,6 +118,103 @@ def test_gradients():
             seen[np.unique(faces[face[b][face[b] >= 0]])] = True
         assert (~seen).any() and not c32['dpos'][:, ~seen].any() and not c64['dattr'][..., ~seen, :].any()
         assert not c64['dpos'][..., 2].any()
+
+
+def test_run_length_cases():
+    """the scaled triangle covers exactly 1, 2, 63, 64, 65, 127, 128, 129 and 193 pixels, one face each, at the scales the sweep found"""
+    cases = R.run_length_cases()
+    assert tuple(cases) == R.RUN_LENGTHS == (1, 2, 63, 64, 65, 127, 128, 129, 193)
+    for n, (s, pos, f) in cases.items():
+        r = R.raster(pos, f, 32, 32, np.float32)
+        got = int((r['face'] >= 0).sum())
+        print(f'run of {n}: scale {s:.4f}, {got} covered pixels')
+        assert got == n and pos.dtype == np.float32 and len(f) == 1
+        assert np.array_equal(pos[:, 2:], R.triangle_cases()['tri012'][0][:, 2:])          # z and w kept
+    runs = sorted(int(R.backward_case(f'run_{n}')['runs'][0]) for n in R.RUN_LENGTHS)
+    print(f'triangle family: runs {runs}')
+    assert 64 in runs and 65 in runs and max(runs) >= 129
+
+
+# what every case was built for, as a predicate of its pixels-per-(view, face) histogram `runs` (and the case)
+def _every_tile_is_touched(c):
+    """a face with a corner at w <= 0 has no pixel box: its record is walked by every tile of the image"""
+    rec = R.setup(list(c['pos'][0]), c['faces'][0], c['H'], c['W'], np.float32)
+    return bool((c['pos'][0, :, 3] <= 0).any()) and rec[5] == (0, 0, c['W'] - 1, c['H'] - 1)
+
+
+def _pixels_per_face(c):
+    face = c['r32']['face']
+    return np.bincount(face[face >= 0], minlength=len(c['faces']))
+
+
+BUILT_FOR = {
+    'w_negative_130x70': lambda runs, c: len(runs) == 1 and runs[0] > 64 * 64 and c['H'] % 8 != 0 and c['W'] % 8 != 0 and _every_tile_is_touched(c),
+    'w_negative_32x32': lambda runs, c: len(runs) == 1 and runs[0] > 129,
+    'tri012_37x53': lambda runs, c: len(runs) == 1 and runs[0] > 129 and c['H'] != c['W'],
+    # counted per face over both views, 23 faces own more than 64 pixels (the largest 104); a run of the kernels is per (view, face),
+    # and of those only 2 are above 64 here (the largest 70).  The sphere at 136 x 200 is the case with many long runs of one mesh.
+    'sphere2_200x136': lambda runs, c: int((_pixels_per_face(c) > 64).sum()) >= 20 and int((runs > 64).sum()) >= 2 and int((runs == 1).sum()) >= 1,
+    'sphere2_136x200': lambda runs, c: int((runs > 64).sum()) >= 20 and int(runs.max()) > 128 and int((runs == 1).sum()) >= 1 and c['pos'].shape[0] == 2,
+    'sphere3_37x53': lambda runs, c: c['pos'].shape[0] == 3 and len(runs) > 100,
+    'sphere2_9x7': lambda runs, c: int(runs.sum()) == 12 and int(runs.max()) == 1,
+    'sphere_1x1': lambda runs, c: len(runs) == 0 and int((c['r32']['face'] >= 0).sum()) == 0,
+    'stacked_32x32': lambda runs, c: len(runs) > 1 and len(c['faces']) == 300,
+    'open_37x53': lambda runs, c: len(runs) > 20 and int(c['faces'].max()) < c['pos'].shape[1] - 3,
+}
+
+
+@pytest.mark.parametrize('name', R.BACKWARD_CASES)
+def test_backward_case_classification(name):
+    """every case of the backward passes: the float32 restatement returns the float64 face on decided pixels, the undecided share stays
+    under the cap, and the histogram of pixels per face holds what the case was built for"""
+    c = R.backward_case(name)
+    r32, r64, runs = c['r32'], c['r64'], c['runs']
+    undecided = float((~r64['decided']).mean())
+    wrong = int(((r32['face'] != r64['face']) & r64['decided']).sum())
+    covered = [int((m >= 0).sum()) for m in r32['face']]
+    print(f'{name}: {c["H"]} x {c["W"]}, covered {covered} of {c["H"] * c["W"]} per view, {len(runs)} (view, face) runs, largest {int(runs.max()) if len(runs) else 0}, '
+          f'{int((runs > 64).sum())} above 64, {int((runs == 1).sum())} of one pixel, undecided {undecided:.4%}, wrong faces on decided pixels {wrong}')
+    assert undecided <= UNDECIDED_CAP and wrong == 0
+    assert int(runs.sum()) == sum(covered)
+    if name.startswith('run_'):
+        assert runs.tolist() == [int(name[4:])]
+    else:
+        assert BUILT_FOR[name](runs, c), name
+    if name == 'open_37x53':
+        pos, f = c['pos'][0], c['faces']
+        edges = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), 1)
+        _, count = np.unique(edges, axis=0, return_counts=True)
+        boundary = int((count == 1).sum())
+        used = np.zeros(len(pos), bool)
+        used[f.reshape(-1)] = True
+        print(f'{name}: {boundary} boundary edges of {len(count)}, {int((~used).sum())} vertices no face references')
+        assert boundary > len(f) and int((~used).sum()) >= 3 and not used[-3:].any()
+
+
+@pytest.mark.parametrize('name,A', R.BACKWARD_PARAMS)
+@pytest.mark.parametrize('kind', ['shared', 'per_view'])
+def test_backward_references(name, A, kind):
+    """the closed forms in float64 equal float64 autograd to 1e-9; the kernel-order float32 restatement — what the device must equal bit
+    for bit — stays under the 10 x rule against float32 and float64 autograd"""
+    c, g = R.backward_case(name), R.backward_reference(name, A, kind)
+    a32, a64, k32 = g['a32'], g['a64'], g['kernel']
+    c64 = R.grads_closed(c['pos'], c['faces'], a64['uv'], c['r32']['face'], c['duv'], g['attr'], g['dout'], np.float64)
+    rels = {k: float(np.abs(c64[k] - a64[k]).max() / max(float(np.abs(a64[k]).max()), 1e-300)) for k in ('dpos', 'dattr', 'duv_interp')}
+    for k, rel in rels.items():
+        print(f'{name} A={A} {kind} {k}: closed form against float64 autograd, relative {rel:.2e}')
+    for k, rel in rels.items():
+        assert rel <= 1e-9, (name, kind, k)
+    for k in ('dpos', 'dattr', 'duv_interp'):
+        assert k32[k].dtype == np.float32 and k32[k].shape == a64[k].shape
+        parity(f'{name} A={A} {kind} {k} kernel order', k32[k], a32[k], a64[k])
+    pos, faces, face = c['pos'], c['faces'], c['r32']['face']
+    for b in range(pos.shape[0]):
+        seen = np.zeros(pos.shape[1], bool)
+        seen[np.unique(faces[face[b][face[b] >= 0]])] = True
+        assert not k32['dpos'][b, ~seen].any() and (kind == 'shared' or not k32['dattr'][b, ~seen].any())
+    assert not k32['dpos'][..., 2].any() and not k32['duv_interp'][face < 0].any()
+    if name == 'sphere_1x1':
+        assert not any(k32[k].any() for k in ('dpos', 'dattr', 'duv_interp'))
 
 
 @pytest.mark.parametrize('sanitize', (False, True), ids=('plain', 'sanitized'))
