@@ -972,6 +972,37 @@ int ra_rasterize_backward(ra_ctx* ctx, const ra_topo* topo, const float* pos_dev
  * 2 the largest channel count */
 int ra_raster_tile(int which);
 
+/* ---- silhouette antialiasing: what the reference's render_nvdiffrast asks of dr.antialias, with position gradients ----
+ * color_dev B x H x W x C fp32 (C >= 1, no upper bound), zw_dev / face_dev: ra_rasterize's maps of the same views, pos_dev B x n_verts x 4
+ * the clip-space positions they were rasterised from, topo: a topology of the same face list -> out_dev B x H x W x C.
+ * The rule is csrc/ra_antialias_rules.hpp's, this project's statement of Laine et al. 2020 section 3.4, one named fp32 operation per
+ * rounding.  A PAIR is two 4-adjacent pixels with different face ids.  Its OWN pixel is the covered one, or the winner of the depth
+ * rule (z/w, face id).  Among the three edges of the own pixel's face, ascending, the first one counts whose ends have w > 0, that
+ * straddles the line through the own centre along the pair's axis, whose crossing lies at d in [0, 1] pixels from the own centre
+ * towards the other pixel, and that is a silhouette in this view (not exactly two half-edges, a dropped twin face, or both faces on the
+ * same side of it); alpha = d - 0.5.  alpha >= 0: out[other] += alpha (in[own] - in[other]); else out[own] += -alpha (in[other] -
+ * in[own]); always from the INPUT colours.  A pixel adds its pairs in the order left, right, up, down.  A face id outside [-1, F) makes
+ * its pairs inert.  Deviations from nvdiffrast: no fixed-point snapping, and only the own pixel's face is searched (as in the paper).
+ * ra_antialias: one thread per (pixel, four channels) gathers its four pairs — both pixels of a pair evaluate the same function of the
+ * pair and get the same bits.  No atomics, asynchronous, NO read-back.  B x H x W == 0 writes nothing; an empty topology copies color.
+ * ra_antialias_backward: dout_dev B x H x W x C -> dcolor_dev (nullable; the transposed gather) and dpos_dev (nullable; B x n_verts x 4,
+ * the z component 0), the face map and the set of active pairs held fixed; pos_gradient_boost multiplies dpos only (the finished sum).
+ * Reduction order of dpos: no float atomics.  Every pair slot (view, 2 pixel + axis) gets the key (view, half-edge of its edge, slot);
+ * the active ones are compacted in ascending slot order and their number is read back — the ONE blocking read-back of the backward
+ * (4 bytes, only with dpos; it sizes the sort and the launch); one radix sort of the active keys groups them by (view, half-edge); one
+ * wave per run adds d L / d C of its pairs in ascending order per lane (pairs l, l + 64, ...) and the lanes in the fixed xor tree 32,
+ * 16, .., 1, and writes the gradients of the half-edge's two ends to zeroed scratch; a vertex pass adds, over the vertex's outgoing
+ * half-edges in ascending order, the tail term of each and then the head term of the half-edge before it in its face.  Row b of dpos
+ * depends on view b alone; the same bits every time.  Otherwise asynchronous.  Scratch belongs to the ctx and only grows.  Outputs of
+ * no elements may be null.
+ * Errors: "null argument", "bad sizes" (C >= 1, B x H x W x C < 2^31, n_verts of the topology; with dpos B x H x W < 2^30), "not a
+ * topology of this ctx". */
+int ra_antialias(ra_ctx* ctx, const ra_topo* topo, const float* color_dev, int C, const float* pos_dev, int B, int n_verts, const float* zw_dev,
+                 const int* face_dev, int H, int W, float* out_dev, void* stream);
+int ra_antialias_backward(ra_ctx* ctx, const ra_topo* topo, const float* color_dev, int C, const float* pos_dev, int B, int n_verts, const float* zw_dev,
+                          const int* face_dev, int H, int W, const float* dout_dev, float pos_gradient_boost, float* dcolor_dev, float* dpos_dev,
+                          void* stream);
+
 /* ---- mesh extraction: the two steps the reference's mesh renderer leaves to mcubes and trimesh (mesh_renderer.py:74-84) ----
  * ra_marching_cubes: classic marching cubes on a DEVICE volume of nx x ny x nz fp32 values, x slowest (what reshape gives), with the
  * classic corner and edge numbering, 256-entry tables derived by rule (relightableavatar_amd/mcubes_tables.py) and linear

@@ -217,6 +217,10 @@ SYMBOLS = {
                                 [C.c_void_p] * 4),
     'ra_rasterize_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'ra_raster_tile': (C.c_int, [C.c_int]),
+    'ra_antialias': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                               C.c_void_p]),
+    'ra_antialias_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ra_ray_tri_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     'ra_sdf_volume': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                 C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

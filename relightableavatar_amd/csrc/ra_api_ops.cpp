@@ -7,6 +7,7 @@
 #include "ra_fit_rules.hpp"
 #include "ra_cloth_rules.hpp"
 #include "ra_raster_rules.hpp"
+#include "ra_antialias.hpp"
 #include <cmath>
 #include <cstring>
 
@@ -1360,6 +1361,88 @@ int ra_rasterize_backward(ra_ctx* c, const ra_topo* topo, const float* pos, int 
     RasterBwdJob j{};
     j.pos = pos; j.uv = uv; j.duv = duv; j.B = B; j.H = H; j.W = W; j.dpos = dpos;
     launch_rasterize_backward(j, t, sorted, g_face, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- silhouette antialiasing (ra_antialias.hip) ----------------------------------------------------
+static bool antialias_sizes_ok(int C, int B, int V, int H, int W) {
+    return C >= 1 && B >= 0 && V >= 0 && H >= 0 && W >= 0 && (long long)B * H < (1ll << 31) && (long long)B * H * W < (1ll << 31) &&
+           (long long)B * H * W * C < (1ll << 31);
+}
+
+int ra_antialias(ra_ctx* c, const ra_topo* topo, const float* color, int C, const float* pos, int B, int V, const float* zw, const int* face, int H, int W,
+                 float* out, void* stream) {
+    RA_CHECK(antialias_sizes_ok(C, B, V, H, W), "ra_antialias: bad sizes (C >= 1, B, H, W >= 0, B x H x W x C < 2^31)");
+    RA_CHECK(c && topo, "ra_antialias: null argument");
+    RA_CHECK(find_topo(c, topo), "ra_antialias: not a topology of this ctx");
+    const TopoView& t = topo->view;
+    RA_CHECK(V == t.n_verts, "ra_antialias: bad sizes (n_verts of the topology)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    const size_t n = (size_t)B * H * W * C;
+    if (n == 0) return 0;
+    RA_CHECK(color && out, "ra_antialias: null argument (color, out)");
+    if (t.n_faces == 0) {
+        RA_HIP(hipMemcpyAsync(out, color, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+    RA_CHECK(pos && zw && face, "ra_antialias: null argument (pos, zw, face)");
+    AaJob j{};
+    j.color = color; j.pos = pos; j.zw = zw; j.face = face; j.B = B; j.H = H; j.W = W; j.C = C;
+    launch_antialias_gather(j, t, nullptr, out, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_antialias_backward(ra_ctx* c, const ra_topo* topo, const float* color, int C, const float* pos, int B, int V, const float* zw, const int* face, int H,
+                          int W, const float* dout, float pos_gradient_boost, float* dcolor, float* dpos, void* stream) {
+    RA_CHECK(antialias_sizes_ok(C, B, V, H, W), "ra_antialias_backward: bad sizes (C >= 1, B, H, W >= 0, B x H x W x C < 2^31)");
+    RA_CHECK(c && topo, "ra_antialias_backward: null argument");
+    RA_CHECK(find_topo(c, topo), "ra_antialias_backward: not a topology of this ctx");
+    const TopoView& t = topo->view;
+    const long long n_pix = (long long)B * H * W;
+    RA_CHECK(V == t.n_verts && (!dpos || (n_pix < (1ll << 30) && (long long)B * t.n_faces < (1ll << 29) &&
+                                          (double)B * 3.0 * t.n_faces * 2.0 * H * W < 9.0e18)),
+             "ra_antialias_backward: bad sizes (n_verts of the topology; with dpos B x H x W < 2^30, B x F < 2^29, 6 B F H W < 2^63)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    const size_t n = (size_t)n_pix * C;
+    if (n == 0 || t.n_faces == 0) {             // no pixel or no face: no pair.  An output of no elements may be null
+        if (dcolor && n > 0) {
+            RA_CHECK(dout, "ra_antialias_backward: null argument (dout)");
+            RA_HIP(hipMemcpyAsync(dcolor, dout, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+        if (dpos && (size_t)B * V > 0) RA_HIP(hipMemsetAsync(dpos, 0, (size_t)B * V * 4 * sizeof(float), s));
+        return 0;
+    }
+    RA_CHECK(dcolor || dpos, "ra_antialias_backward: null argument");
+    RA_CHECK(color && pos && zw && face && dout, "ra_antialias_backward: null argument (color, pos, zw, face, dout)");
+    AaJob j{};
+    j.color = color; j.pos = pos; j.zw = zw; j.face = face; j.B = B; j.H = H; j.W = W; j.C = C;
+    if (dcolor) launch_antialias_gather(j, t, dout, dcolor, s);
+    if (dpos) {
+        int err = 0;
+        size_t tb = antialias_temp_bytes(2 * n_pix, 0);
+        unsigned long long* keys = c->buf<unsigned long long>("antialias_keys", 2 * (size_t)n_pix, &err);
+        unsigned long long* compact = c->buf<unsigned long long>("antialias_keys_active", 2 * (size_t)n_pix, &err);
+        int* count = c->buf<int>("antialias_count", 1, &err);
+        void* temp = c->buf<char>("antialias_tmp", tb + 16, &err);
+        float* g_he = c->buf<float>("antialias_g_he", (size_t)B * t.n_faces * 18, &err);
+        RA_CHECK(!err, "ra_antialias_backward: out of device memory");
+        RA_CHECK(launch_antialias_keys(j, t, keys, compact, count, temp, tb, s) == 0, "ra_antialias_backward: device compaction failed");
+        RA_HIP(hipGetLastError());
+        int n_active = 0;           // the one read-back: the number of active pairs, which sizes the sort and the run pass
+        RA_HIP(hipMemcpyAsync(&n_active, count, sizeof(int), hipMemcpyDeviceToHost, s));
+        RA_HIP(hipStreamSynchronize(s));
+        RA_CHECK(n_active >= 0 && n_active <= 2 * n_pix, "ra_antialias_backward: device compaction failed");
+        tb = antialias_temp_bytes(0, n_active);
+        unsigned long long* sorted = c->buf<unsigned long long>("antialias_keys_sorted", (size_t)n_active + 1, &err);
+        temp = c->buf<char>("antialias_sort_tmp", tb + 16, &err);
+        RA_CHECK(!err, "ra_antialias_backward: out of device memory");
+        RA_CHECK(launch_antialias_dpos(j, t, dout, pos_gradient_boost, compact, sorted, n_active, temp, tb, g_he, dpos, s) == 0,
+                 "ra_antialias_backward: device sort failed");
+    }
     RA_HIP(hipGetLastError());
     return 0;
 }

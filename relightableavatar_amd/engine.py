@@ -1041,6 +1041,49 @@ class Engine:
                                              _ptr(out) if out.numel() else None, self.stream), 'ra_rasterize_backward')
         return out
 
+    def _antialias_args(self, who, color, raster, pos_clip):
+        d = self.device
+        col, pos = _f32(color, d), _f32(pos_clip, d)
+        pos = pos[None] if pos.ndim == 2 else pos
+        zw, face = _f32(raster.zw, d), raster.face.detach().to(device=d, dtype=torch.int32).contiguous()
+        if col.ndim != 4 or face.shape != col.shape[:3] or zw.shape != face.shape or pos.ndim != 3 or pos.shape[0] != col.shape[0] or pos.shape[2] != 4:
+            raise ValueError(f'{who}: color must be (B, H, W, C), raster.zw and raster.face (B, H, W) and pos_clip (B, V, 4)')
+        return col, pos, zw, face
+
+    def antialias(self, topology, color, raster, pos_clip):
+        """color (B,H,W,C) float32, C >= 1; raster: Engine.rasterize's dotdict (zw, face) of pos_clip (B,V,4); topology: Engine.topology of
+        the same faces -> (B,H,W,C) float32 on the device with the silhouettes blended (include/relightableavatar.h: ra_antialias,
+        DESIGN.md section 26).  A gather per pixel: no atomics, the same bits every time.  Nothing is read back."""
+        col, pos, zw, face = self._antialias_args('Engine.antialias', color, raster, pos_clip)
+        B, H, W, Cn = col.shape
+        out = torch.empty_like(col)
+        check(self.lib.ra_antialias(self.ctx, topology._handle, _ptr(col) if col.numel() else None, Cn, _ptr(pos) if pos.numel() else None, B, pos.shape[1],
+                                    _ptr(zw) if zw.numel() else None, _ptr(face) if face.numel() else None, H, W, _ptr(out) if out.numel() else None,
+                                    self.stream), 'ra_antialias')
+        return out
+
+    def antialias_backward(self, topology, color, raster, pos_clip, dout, pos_gradient_boost=1.0, want=('dcolor', 'dpos')):
+        """the gradient of Engine.antialias, the face map and the set of active pairs held fixed: dout (B,H,W,C) -> dotdict(dcolor (B,H,W,C),
+        dpos (B,V,4) with a zero z component) on the device (ra_antialias_backward).  pos_gradient_boost multiplies dpos only.  No float
+        atomics: the same bits every time, and row b of dpos depends on view b alone.  One 4-byte read-back with dpos (the number of
+        active pairs), none without."""
+        col, pos, zw, face = self._antialias_args('Engine.antialias_backward', color, raster, pos_clip)
+        g = _f32(dout, self.device)
+        B, H, W, Cn = col.shape
+        if g.shape != col.shape:
+            raise ValueError(f'Engine.antialias_backward: dout must be ({B}, {H}, {W}, {Cn})')
+        out = dotdict()
+        if 'dcolor' in want:
+            out.dcolor = torch.empty_like(col)
+        if 'dpos' in want:
+            out.dpos = torch.empty_like(pos)
+        opt = lambda t: _ptr(t) if t is not None and t.numel() else None
+        if not want:
+            return out
+        check(self.lib.ra_antialias_backward(self.ctx, topology._handle, opt(col), Cn, opt(pos), B, pos.shape[1], opt(zw), opt(face), H, W, opt(g),
+                                             float(pos_gradient_boost), _ptr(out.get('dcolor')), _ptr(out.get('dpos')), self.stream), 'ra_antialias_backward')
+        return out
+
     def cloth(self, topology, rest_verts, vm, fm, material=None):
         """topology (Engine.topology), rest_verts (V,3), vm (M,2) material coordinates, fm (F,3) integers into vm, material (an
         object or dict with density, thickness, young_modulus, poisson_ratio, bending_multiplier, stretch_multiplier and optionally

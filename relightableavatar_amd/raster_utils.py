@@ -1,12 +1,15 @@
-"""The reference's lib/utils/raster_utils.py on the device rasteriser (Engine.rasterize / Engine.interpolate).
+"""The reference's lib/utils/raster_utils.py on the device rasteriser (Engine.rasterize / Engine.interpolate / Engine.antialias, DESIGN.md
+sections 25 and 26).
 
-The camera helpers are the reference's torch arithmetic.  `rasterize` and `interpolate` are autograd ops over the HIP kernels, first
-order only, in nvdiffrast's layouts.  `render_nvdiffrast` is the reference's ATTRIBUTE path.
+The camera helpers are the reference's torch arithmetic.  `rasterize`, `interpolate` and `antialias` are autograd ops over the HIP
+kernels, first order only, in nvdiffrast's layouts and argument order.  `render_nvdiffrast` is the reference's ATTRIBUTE path.
 
-Deliberate limits (DESIGN.md sections 6 and 25):
+Deliberate limits (DESIGN.md sections 6, 25 and 26):
   * the texture path (uv / img, dr.texture, mip maps, rast_db) raises NotImplementedError;
-  * dr.antialias is not built: render_nvdiffrast skips that step, the soft mask comes from R_S supersampling alone, position gradients
-    flow through the interpolated attributes only and no gradient arises at silhouettes;
+  * `antialias` is this project's statement of the published algorithm (Laine et al. 2020, section 3.4; csrc/ra_antialias_rules.hpp), not
+    a reproduction of nvdiffrast's output: no fixed-point snapping, and only the own pixel's face is searched for silhouette edges, as
+    in the paper.  render_nvdiffrast applies it only with antialias=True (the reference's behaviour); by default it skips that step, the
+    soft mask comes from R_S supersampling alone and no gradient arises at silhouettes;
   * no depth peeling, no range mode, no scissor;
   * the sampling rules are this project's (csrc/ra_raster_rules.hpp), not nvdiffrast's fixed-point snapping.
 """
@@ -141,6 +144,28 @@ class _Interpolate(torch.autograd.Function):
         return dattr, drast, None, None, None
 
 
+class _Antialias(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, color, rast, pos, faces, boost, engine, topology):
+        topo = topology if topology is not None else engine.topology(faces, pos.shape[-2])
+        out = engine.antialias(topo, color, _split(rast), pos)
+        ctx.save_for_backward(color.detach(), rast.detach(), pos.detach())
+        # a topology made here lives as long as the graph: the backward reuses it instead of building a second one
+        ctx.engine, ctx.topology, ctx.boost = engine, topo, boost
+        ctx.like = (color.dtype, color.device, pos.shape, pos.dtype, pos.device)
+        return out.to(device=color.device)
+
+    @staticmethod
+    def backward(ctx, g):
+        color, rast, pos = ctx.saved_tensors
+        want = tuple(k for k, need in zip(('dcolor', 'dpos'), (ctx.needs_input_grad[0], ctx.needs_input_grad[2])) if need)
+        c_dtype, c_device, p_shape, p_dtype, p_device = ctx.like
+        d = ctx.engine.antialias_backward(ctx.topology, color, _split(rast), pos, g, pos_gradient_boost=ctx.boost, want=want) if want else dotdict()
+        dcolor = d.dcolor.to(device=c_device, dtype=c_dtype) if 'dcolor' in d else None
+        dpos = d.dpos.reshape(p_shape).to(device=p_device, dtype=p_dtype) if 'dpos' in d else None
+        return dcolor, None, dpos, None, None, None, None
+
+
 def rasterize(pos: torch.Tensor, faces: torch.Tensor, H: int, W: int, engine=None, topology=None) -> torch.Tensor:
     """pos (B,V,4) clip-space positions, faces (F,3) -> nvdiffrast's (B,H,W,4) float32 on the device: u, v, z/w, face + 1 (0 where the
     pixel is empty).  Differentiable in pos through u and v with the face map held fixed (first order); z/w and the face carry no
@@ -158,14 +183,28 @@ def interpolate(attrs: torch.Tensor, rast: torch.Tensor, faces: torch.Tensor, ra
     return _Interpolate.apply(attrs, rast, faces, _engine(engine), topology)
 
 
+def antialias(color: torch.Tensor, rast: torch.Tensor, pos: torch.Tensor, tri: torch.Tensor, topology_hash=None, pos_gradient_boost: float = 1.0,
+              engine=None, topology=None) -> torch.Tensor:
+    """nvdiffrast's antialias, in its argument order: color (B,H,W,C), rast: rasterize's output, pos (B,V,4) the clip-space positions it was
+    rasterised from, tri (F,3) -> (B,H,W,C) float32 with the silhouettes blended (module docstring).
+    Differentiable in color and in pos (first order, the face map and the set of blended pixel pairs held fixed); pos_gradient_boost
+    multiplies the gradient of pos only.  topology_hash is accepted and ignored; topology: Engine.topology(tri, V), which both passes
+    need — built in the forward when not given (one read-back) and kept for the backward."""
+    if pos.ndim != 3 or pos.shape[-1] != 4:
+        raise ValueError('antialias: pos must be (B, V, 4); the range mode is not supported')
+    return _Antialias.apply(color, rast, pos, tri, float(pos_gradient_boost), _engine(engine), topology)
+
+
 def render_nvdiffrast(verts: torch.Tensor, faces: torch.Tensor, attrs: torch.Tensor = None, uv: torch.Tensor = None, img: torch.Tensor = None,
                       H: int = 512, W: int = 512, R: torch.Tensor = None, T: torch.Tensor = None, K: torch.Tensor = None, R_S: int = 2,
-                      pos_gradient_boost: float = 1.0, engine=None, topology=None):
+                      pos_gradient_boost: float = 1.0, engine=None, topology=None, antialias: bool = False):
     """The reference's render_nvdiffrast, attribute path: verts (B,V,3|4) or (V,3) with R, faces (F,3), attrs (B,V,A) or (V,A), R (B,3,3),
     T (B,3,1), K (B,4,4) clip matrix (None: the reference's default) -> (rast_attrs (B,H,W,A), rast_msk (B,H,W)).  One mesh is expanded
-    over the views of R; the maps are rasterised at R_S times the size and resized bilinearly.  dr.antialias is NOT applied (module
-    docstring): the mask is soft through R_S alone and carries no gradient; pos_gradient_boost is accepted and unused.
-    uv / img (the texture path) raise NotImplementedError."""
+    over the views of R; the maps are rasterised at R_S times the size and resized bilinearly.
+    antialias=True is the REFERENCE'S behaviour: `antialias` (this module) is applied to cat([attributes, mask]) before the resize with
+    pos_gradient_boost, so the mask is fractional along the outline and carries a gradient to verts.  The default False skips that step
+    (the values this call returned before the op existed): the mask is soft through R_S alone, carries no gradient, and
+    pos_gradient_boost is unused.  uv / img (the texture path) raise NotImplementedError."""
     if uv is not None or img is not None:
         raise NotImplementedError('render_nvdiffrast: the texture path (uv, img: dr.texture, mip maps, rast_db) is not supported')
     assert attrs is not None
@@ -194,6 +233,8 @@ def render_nvdiffrast(verts: torch.Tensor, faces: torch.Tensor, attrs: torch.Ten
     rend_msk = rast[:, :, :, 3] != 0
     pattrs = interpolate(attrs, rast, faces, engine=engine, topology=topology)
     aa = torch.cat([pattrs, rend_msk.view(rast.shape[0], R_H, R_W, 1).to(pattrs.dtype)], dim=-1)
+    if antialias:
+        aa = _Antialias.apply(aa, rast, ndcverts, faces, float(pos_gradient_boost), _engine(engine), topology)
     aa = bilinear_interpolation(aa, [H, W])
     rast_attrs, rast_msk = aa.split([A, 1], dim=-1)
     return rast_attrs, rast_msk[..., 0]
