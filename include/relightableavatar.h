@@ -1003,6 +1003,47 @@ int ra_antialias_backward(ra_ctx* ctx, const ra_topo* topo, const float* color_d
                           const int* face_dev, int H, int W, const float* dout_dev, float pos_gradient_boost, float* dcolor_dev, float* dpos_dev,
                           void* stream);
 
+/* ---- the texture path: what the reference's render_nvdiffrast asks of dr.interpolate(rast_db=, diff_attrs=) and dr.texture ----
+ * The rule is csrc/ra_texture_rules.hpp's, this project's statement of Laine et al. 2020 section 3.3, one named fp32 operation per
+ * rounding: pixel differentials of the barycentrics, a 2 x 2-mean mip chain, a level of detail from the squared major axis of the
+ * pixel's footprint (its log2 is a fixed polynomial: the same bits on the host and the device), bilinear / trilinear / nearest taps
+ * with wrap or clamp.  A uv that is not finite (or beyond 2^30 texels) gives 0 and no gradient.  No entry point reads anything back.
+ * ra_raster_db: pos_dev B x n_verts x 4, faces_dev n_faces x 3, face_dev B x H x W (ra_rasterize's) -> rast_db_dev B x H x W x 4 =
+ *   (du/dX, du/dY, dv/dX, dv/dY), 0 where the pixel is empty.  One lane per pixel.
+ * ra_interpolate_da: attr_dev (n_verts x A, or B x n_verts x A with per_view), channels: n HOST ints in [0, A), 1 <= n <= 64 ->
+ *   out_da_dev B x H x W x 2n = (da_0/dX, da_0/dY, da_1/dX, ...).  Forward only.
+ * ra_texture_mips: the chain of tex_dev Bt x TH x TW x C into mips_dev, Bt x offsets[*lmax + 1] x C floats, level l of texture t at
+ *   (t offsets[*lmax + 1] + offsets[l]) C, level 0 included.  offsets: RA_TEX_MAX_LEVELS + 1 HOST entries; they and *lmax are host
+ *   arithmetic from the sizes alone, and with mips_dev == NULL nothing else happens (ctx and tex_dev may be null).
+ * ra_texture: tex_dev Bt x TH x TW x C (Bt = 1: shared by the views, or B), row 0 at v = 0; uv_dev B x H x W x 2; uv_da_dev B x H x W x 4
+ *   (needed by RA_TEX_FILTER_TRILINEAR alone, else ignored) -> out_dev B x H x W x C.  A per-pixel gather.
+ * ra_texture_backward: dout_dev B x H x W x C -> duv_dev B x H x W x 2 (nullable) and dtex_dev Bt x TH x TW x C (nullable), first
+ *   order: the texel cells, the level pair and lod held fixed, no gradient to uv_da.  dtex uses no float atomics: the tap slots
+ *   (view, pixel, tap) are sorted by (view, level, texel), one wave sums a run in a fixed lane and tree order, a last pass folds the
+ *   chain into level 0 and adds the views of a shared texture in ascending order: the same bits every time, and row t of a per-view
+ *   dtex depends on view t alone.  The tap count is not compacted.  Scratch belongs to the ctx and only grows.
+ * Errors, all named before the ctx is touched: "bad sizes" (Bt = 1 or B, 1 <= TH, TW <= 32768, 1 <= C <= 64, max_mip_level >= 0,
+ * Bt x TH x TW x C < 2^31, B x H x W x C < 2^31; with dtex the tap-count limit B x H x W x taps < 2^31 - 1, taps = 1 / 4 / 8 for
+ * nearest / linear / trilinear), "unknown mode", "null argument". */
+#define RA_TEX_FILTER_NEAREST 0
+#define RA_TEX_FILTER_LINEAR 1
+#define RA_TEX_FILTER_TRILINEAR 2       /* nvdiffrast's linear-mipmap-linear */
+#define RA_TEX_BOUNDARY_WRAP 0
+#define RA_TEX_BOUNDARY_CLAMP 1
+#define RA_TEX_MAX_LEVELS 16
+int ra_raster_db(ra_ctx* ctx, const float* pos_dev, int B, int n_verts, const int* faces_dev, int n_faces, const int* face_dev, int H, int W,
+                 float* rast_db_dev, void* stream);
+int ra_interpolate_da(ra_ctx* ctx, const float* attr_dev, int per_view, int n_verts, int A, const int* faces_dev, int n_faces, const int* face_dev,
+                      const float* rast_db_dev, int B, int H, int W, const int* channels, int n, float* out_da_dev, void* stream);
+int ra_texture_mips(ra_ctx* ctx, const float* tex_dev, int Bt, int TH, int TW, int C, int max_mip_level, float* mips_dev, int* lmax, long long* offsets,
+                    void* stream);
+int ra_texture(ra_ctx* ctx, const float* tex_dev, int Bt, int TH, int TW, int C, const float* uv_dev, const float* uv_da_dev, int B, int H, int W,
+               int filter, int boundary, int max_mip_level, float* out_dev, void* stream);
+int ra_texture_backward(ra_ctx* ctx, const float* tex_dev, int Bt, int TH, int TW, int C, const float* uv_dev, const float* uv_da_dev, int B, int H, int W,
+                        int filter, int boundary, int max_mip_level, const float* dout_dev, float* duv_dev, float* dtex_dev, void* stream);
+/* 0: the largest C, 1: RA_TEX_MAX_LEVELS, 2: the largest extent, 3: the channels a wave of the run pass sums per trip */
+int ra_texture_tile(int which);
+
 /* ---- mesh extraction: the two steps the reference's mesh renderer leaves to mcubes and trimesh (mesh_renderer.py:74-84) ----
  * ra_marching_cubes: classic marching cubes on a DEVICE volume of nx x ny x nz fp32 values, x slowest (what reshape gives), with the
  * classic corner and edge numbering, 256-entry tables derived by rule (relightableavatar_amd/mcubes_tables.py) and linear

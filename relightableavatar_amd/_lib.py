@@ -17,6 +17,9 @@ RA_RAYCAST_BRUTE, RA_RAYCAST_UNSORTED = 1, 2      # flags of ra_mesh_raycast
 # the arrays of ra_topo_array, in the header's order
 RA_TOPO_ARRAYS = ('vert', 'twin', 'edge', 'edges', 'edge_counts', 'edge_he_start', 'edge_he', 'nbr_start', 'nbr', 'out_start', 'out_he')
 RA_RASTER_BRUTE = 1      # flag of ra_rasterize
+RA_TEX_FILTERS = {'nearest': 0, 'linear': 1, 'linear-mipmap-linear': 2}      # the filter and boundary modes of ra_texture
+RA_TEX_BOUNDARIES = {'wrap': 0, 'clamp': 1}
+RA_TEX_MAX_LEVELS = 16
 RA_CLOTH_STRETCH, RA_CLOTH_BENDING, RA_CLOTH_GRAVITY = 1, 2, 4      # terms of ra_cloth_energy
 # the fields of ra_cloth_material in the header's order, with the reference's StVKMaterial defaults
 CLOTH_MATERIAL_DEFAULTS = (('density', 426 * 0.00047), ('thickness', 0.00047), ('young_modulus', 0.7e5), ('poisson_ratio', 0.485),
@@ -221,6 +224,16 @@ SYMBOLS = {
                                C.c_void_p]),
     'ra_antialias_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                         C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ra_raster_db': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_interpolate_da': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_texture_mips': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int),
+                                  C.POINTER(C.c_longlong), C.c_void_p]),
+    'ra_texture': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                             C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_texture_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ra_texture_tile': (C.c_int, [C.c_int]),
     'ra_ray_tri_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     'ra_sdf_volume': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                 C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

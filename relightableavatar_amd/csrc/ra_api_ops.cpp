@@ -8,6 +8,7 @@
 #include "ra_cloth_rules.hpp"
 #include "ra_raster_rules.hpp"
 #include "ra_antialias.hpp"
+#include "ra_texture.hpp"
 #include <cmath>
 #include <cstring>
 
@@ -1442,6 +1443,140 @@ int ra_antialias_backward(ra_ctx* c, const ra_topo* topo, const float* color, in
         RA_CHECK(!err, "ra_antialias_backward: out of device memory");
         RA_CHECK(launch_antialias_dpos(j, t, dout, pos_gradient_boost, compact, sorted, n_active, temp, tb, g_he, dpos, s) == 0,
                  "ra_antialias_backward: device sort failed");
+    }
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the texture path (ra_texture.hip) ------------------------------------------------------------
+int ra_texture_tile(int which) { return which == 0 ? TEX_MAX_CHANNELS : which == 1 ? TEX_MAX_LEVELS : which == 2 ? TEX_MAX_EXTENT : which == 3 ? TEX_GROUP : 0; }
+
+int ra_raster_db(ra_ctx* c, const float* pos, int B, int V, const int* faces, int F, const int* face, int H, int W, float* rast_db, void* stream) {
+    RA_CHECK(raster_sizes_ok(B, H, W) && (long long)B * H * W < (1ll << 29) && V >= 0 && V < (1 << 29) && F >= 0 && F < RASTER_MAX_FACES,
+             "ra_raster_db: bad sizes (B, H, W >= 1, B x H x W < 2^29, F < 2^24)");
+    RA_CHECK(c && face && rast_db, "ra_raster_db: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    if (F == 0 || V == 0) {
+        RA_HIP(hipMemsetAsync(rast_db, 0, (size_t)B * H * W * 4 * sizeof(float), s));
+        return 0;
+    }
+    RA_CHECK(pos && faces, "ra_raster_db: null argument (pos, faces)");
+    launch_raster_db(pos, B, V, faces, F, face, H, W, rast_db, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_interpolate_da(ra_ctx* c, const float* attr, int per_view, int V, int A, const int* faces, int F, const int* face, const float* rast_db, int B, int H,
+                      int W, const int* channels, int n, float* out_da, void* stream) {
+    RA_CHECK(raster_sizes_ok(B, H, W) && V >= 0 && V < (1 << 29) && F >= 0 && F < RASTER_MAX_FACES && A >= 1 && (long long)B * V * A < (1ll << 40) && n >= 1 &&
+             n <= TEX_MAX_CHANNELS && (long long)B * H * W * 2 * n < (1ll << 31),
+             "ra_interpolate_da: bad sizes (B, H, W >= 1, F < 2^24, A >= 1, 1 <= n <= 64, B x H x W x 2 n < 2^31)");
+    RA_CHECK(channels && out_da, "ra_interpolate_da: null argument");
+    for (int k = 0; k < n; ++k) RA_CHECK(channels[k] >= 0 && channels[k] < A, "ra_interpolate_da: bad sizes (a selected channel outside [0, A))");
+    RA_CHECK(c, "ra_interpolate_da: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    if (F == 0 || V == 0) {
+        RA_HIP(hipMemsetAsync(out_da, 0, (size_t)B * H * W * 2 * n * sizeof(float), s));
+        return 0;
+    }
+    RA_CHECK(attr && faces && face && rast_db, "ra_interpolate_da: null argument (attr, faces, face, rast_db)");
+    TexDaJob j{};
+    j.attr = attr; j.faces = faces; j.face = face; j.rast_db = rast_db; j.per_view = per_view != 0; j.V = V; j.A = A; j.F = F; j.B = B; j.H = H; j.W = W; j.n = n;
+    for (int k = 0; k < n; ++k) j.ch[k] = channels[k];
+    launch_interpolate_da(j, out_da, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+static bool texture_tex_ok(int Bt, int TH, int TW, int C, int max_mip_level) {
+    return Bt >= 1 && TH >= 1 && TW >= 1 && TH <= TEX_MAX_EXTENT && TW <= TEX_MAX_EXTENT && C >= 1 && C <= TEX_MAX_CHANNELS && max_mip_level >= 0 &&
+           (long long)Bt * TH * TW * C < (1ll << 31);
+}
+
+int ra_texture_mips(ra_ctx* c, const float* tex, int Bt, int TH, int TW, int C, int max_mip_level, float* mips, int* lmax, long long* offsets, void* stream) {
+    RA_CHECK(texture_tex_ok(Bt, TH, TW, C, max_mip_level),
+             "ra_texture_mips: bad sizes (Bt >= 1, 1 <= TH, TW <= 32768, 1 <= C <= 64, max_mip_level >= 0, Bt x TH x TW x C < 2^31)");
+    RA_CHECK(lmax && offsets, "ra_texture_mips: null argument");
+    TexLevels L;
+    texture_levels(TH, TW, max_mip_level, L);
+    *lmax = L.n - 1;
+    for (int l = 0; l <= L.n; ++l) offsets[l] = L.off[l];
+    if (!mips) return 0;                // the sizes alone
+    RA_CHECK(c && tex, "ra_texture_mips: null argument (ctx, tex)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    const long long total = L.off[L.n] * C, level0 = L.off[1] * C;
+    for (int bt = 0; bt < Bt; ++bt)
+        RA_HIP(hipMemcpyAsync(mips + (long long)bt * total, tex + (long long)bt * level0, (size_t)level0 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    for (int l = 1; l < L.n; ++l) launch_texture_mip(mips + L.off[l - 1] * C, total, mips + L.off[l] * C, total, Bt, L.h[l], L.w[l], C, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+// the job of ra_texture and ra_texture_backward: the chain of a trilinear call goes to the ctx's scratch
+static int texture_job(ra_ctx* c, const char* who, const float* tex, int Bt, int TH, int TW, int C, const float* uv, const float* uv_da, int B, int H, int W,
+                       int filter, int boundary, int max_mip_level, TexJob* j, hipStream_t s) {
+    j->tex = tex; j->uv = uv; j->uv_da = uv_da; j->Bt = Bt; j->B = B; j->H = H; j->W = W; j->C = C; j->filter = filter; j->boundary = boundary;
+    texture_levels(TH, TW, filter == TEX_TRILINEAR ? max_mip_level : 0, j->L);
+    if (j->L.n > 1) {
+        int err = 0;
+        const long long stride = (j->L.off[j->L.n] - j->L.off[1]) * C;
+        float* mips = c->buf<float>("texture_mips", (size_t)Bt * stride, &err);
+        if (err) { ra_set_error(std::string(who) + ": out of device memory"); return 1; }
+        launch_texture_mip(tex, j->L.off[1] * C, mips, stride, Bt, j->L.h[1], j->L.w[1], C, s);
+        for (int l = 2; l < j->L.n; ++l)
+            launch_texture_mip(mips + (j->L.off[l - 1] - j->L.off[1]) * C, stride, mips + (j->L.off[l] - j->L.off[1]) * C, stride, Bt, j->L.h[l], j->L.w[l], C, s);
+        j->mips = mips;
+    }
+    return 0;
+}
+
+static bool texture_sizes_ok(int Bt, int TH, int TW, int C, int B, int H, int W, int max_mip_level) {
+    return texture_tex_ok(Bt, TH, TW, C, max_mip_level) && raster_sizes_ok(B, H, W) && (Bt == 1 || Bt == B) && (long long)B * H * W * C < (1ll << 31);
+}
+#define RA_TEXTURE_SIZES "bad sizes (Bt = 1 or B, 1 <= TH, TW <= 32768, 1 <= C <= 64, max_mip_level >= 0, Bt x TH x TW x C < 2^31, B, H, W >= 1, B x H x W x C < 2^31"
+
+int ra_texture(ra_ctx* c, const float* tex, int Bt, int TH, int TW, int C, const float* uv, const float* uv_da, int B, int H, int W, int filter, int boundary,
+               int max_mip_level, float* out, void* stream) {
+    RA_CHECK(texture_sizes_ok(Bt, TH, TW, C, B, H, W, max_mip_level), "ra_texture: " RA_TEXTURE_SIZES ")");
+    RA_CHECK(filter >= TEX_NEAREST && filter <= TEX_TRILINEAR && boundary >= TEX_WRAP && boundary <= TEX_CLAMP, "ra_texture: unknown mode");
+    RA_CHECK(c && tex && uv && out && (uv_da || filter != TEX_TRILINEAR), "ra_texture: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    TexJob j{};
+    if (texture_job(c, "ra_texture", tex, Bt, TH, TW, C, uv, uv_da, B, H, W, filter, boundary, max_mip_level, &j, s)) return 1;
+    launch_texture(j, out, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_texture_backward(ra_ctx* c, const float* tex, int Bt, int TH, int TW, int C, const float* uv, const float* uv_da, int B, int H, int W, int filter,
+                        int boundary, int max_mip_level, const float* dout, float* duv, float* dtex, void* stream) {
+    // the tap-count limit: the B H W T tap slots (T = 1, 4, 8 by filter) are sorted as ONE array of 64-bit keys indexed by an int
+    const long long taps = (long long)B * H * W * texture_taps_per_pixel(filter);
+    TexLevels L;
+    if (TH >= 1 && TW >= 1 && max_mip_level >= 0) texture_levels(TH, TW, filter == TEX_TRILINEAR ? max_mip_level : 0, L); else { L.n = 1; L.off[1] = 1; }
+    RA_CHECK(texture_sizes_ok(Bt, TH, TW, C, B, H, W, max_mip_level) &&
+             (!dtex || (taps < (1ll << 31) - 1 && (double)B * (double)L.off[L.n] * (double)taps < 9.0e18 && (long long)B * L.off[L.n] * C < (1ll << 40))),
+             "ra_texture_backward: " RA_TEXTURE_SIZES "; with dtex B x H x W x taps < 2^31 - 1 (taps 1, 4, 8 by filter) and B x texels x B x H x W x taps < 2^63)");
+    RA_CHECK(filter >= TEX_NEAREST && filter <= TEX_TRILINEAR && boundary >= TEX_WRAP && boundary <= TEX_CLAMP, "ra_texture_backward: unknown mode");
+    RA_CHECK(c && tex && uv && dout && (duv || dtex) && (uv_da || filter != TEX_TRILINEAR), "ra_texture_backward: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    TexJob j{};
+    if (texture_job(c, "ra_texture_backward", tex, Bt, TH, TW, C, uv, uv_da, B, H, W, filter, boundary, max_mip_level, &j, s)) return 1;
+    if (duv) launch_texture_duv(j, dout, duv, s);
+    if (dtex) {
+        int err = 0;
+        const size_t tb = texture_temp_bytes(taps);
+        unsigned long long* keys = c->buf<unsigned long long>("texture_keys", (size_t)taps, &err);
+        unsigned long long* sorted = c->buf<unsigned long long>("texture_keys_sorted", (size_t)taps, &err);
+        void* temp = c->buf<char>("texture_sort_tmp", tb + 16, &err);
+        float* g = c->buf<float>("texture_g", (size_t)B * j.L.off[j.L.n] * C, &err);
+        RA_CHECK(!err, "ra_texture_backward: out of device memory");
+        RA_CHECK(launch_texture_dtex(j, dout, keys, sorted, temp, tb, g, dtex, s) == 0, "ra_texture_backward: device sort failed");
     }
     RA_HIP(hipGetLastError());
     return 0;

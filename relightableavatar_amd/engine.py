@@ -1084,6 +1084,112 @@ class Engine:
                                              float(pos_gradient_boost), _ptr(out.get('dcolor')), _ptr(out.get('dpos')), self.stream), 'ra_antialias_backward')
         return out
 
+    def raster_db(self, pos_clip, faces, raster):
+        """pos_clip (B,V,4) or (V,4), faces (F,3), raster: Engine.rasterize's dotdict (face) of them -> rast_db (B,H,W,4) float32 on the
+        device: the pixel differentials (du/dX, du/dY, dv/dX, dv/dY) of the barycentrics, nvdiffrast's layout, 0 where a pixel is empty
+        (include/relightableavatar.h: ra_raster_db).  Nothing is read back."""
+        d = self.device
+        pos = _f32(pos_clip, d)
+        pos = pos[None] if pos.ndim == 2 else pos
+        face = raster.face.detach().to(device=d, dtype=torch.int32).contiguous()
+        if pos.ndim != 3 or pos.shape[2] != 4 or face.ndim != 3 or face.shape[0] != pos.shape[0]:
+            raise ValueError('Engine.raster_db: pos_clip must be (B, V, 4) or (V, 4) and raster.face (B, H, W)')
+        f = faces.detach().to(device=d, dtype=torch.int32).reshape(-1, 3).contiguous()
+        B, H, W = face.shape
+        out = torch.empty(B, H, W, 4, dtype=torch.float32, device=d)
+        check(self.lib.ra_raster_db(self.ctx, _ptr(pos) if pos.numel() else None, B, pos.shape[1], _ptr(f) if f.numel() else None, f.shape[0], _ptr(face), H, W,
+                                    _ptr(out), self.stream), 'ra_raster_db')
+        return out
+
+    def interpolate_da(self, attrs, raster, faces, rast_db, channels):
+        """attrs (V,A) or (B,V,A), raster: Engine.rasterize's dotdict (face), rast_db: Engine.raster_db's, channels: 1 .. 64 channel
+        indices in [0, A) -> (B,H,W,2n) float32 on the device, (da/dX, da/dY) per selected channel (ra_interpolate_da).  Forward only;
+        nothing is read back."""
+        d = self.device
+        a, db = _f32(attrs, d), _f32(rast_db, d)
+        face = raster.face.detach().to(device=d, dtype=torch.int32).contiguous()
+        B, H, W = face.shape
+        if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[0] != B) or db.shape != (B, H, W, 4):
+            raise ValueError(f'Engine.interpolate_da: attrs must be (V, A) or ({B}, V, A) and rast_db ({B}, {H}, {W}, 4)')
+        ch = [int(c) for c in channels]
+        f = faces.detach().to(device=d, dtype=torch.int32).reshape(-1, 3).contiguous()
+        out = torch.empty(B, H, W, 2 * len(ch), dtype=torch.float32, device=d)
+        check(self.lib.ra_interpolate_da(self.ctx, _ptr(a) if a.numel() else None, int(a.ndim == 3), a.shape[-2], a.shape[-1], _ptr(f) if f.numel() else None,
+                                         f.shape[0], _ptr(face), _ptr(db), B, H, W, (C.c_int * max(len(ch), 1))(*ch), len(ch), _ptr(out), self.stream),
+              'ra_interpolate_da')
+        return out
+
+    def texture_mips(self, tex, max_mip_level=None):
+        """tex (TH,TW,C) or (Bt,TH,TW,C) -> (a list of the chain's levels, each (Bt,h,w,C) float32 on the device, level 0 a copy of tex):
+        level l + 1 is the 2 x 2 mean of level l while both extents are even and above 1 (ra_texture_mips).  Nothing is read back."""
+        t = _f32(tex, self.device)
+        t = t[None] if t.ndim == 3 else t
+        Bt, TH, TW, Cn = t.shape
+        lmax, off = C.c_int(0), (C.c_longlong * (_lib.RA_TEX_MAX_LEVELS + 1))()
+        mm = _lib.RA_TEX_MAX_LEVELS - 1 if max_mip_level is None else int(max_mip_level)
+        check(self.lib.ra_texture_mips(None, None, Bt, TH, TW, Cn, mm, None, C.byref(lmax), off, self.stream), 'ra_texture_mips')
+        total = off[lmax.value + 1]
+        buf = torch.empty(Bt, total, Cn, dtype=torch.float32, device=self.device)
+        check(self.lib.ra_texture_mips(self.ctx, _ptr(t), Bt, TH, TW, Cn, mm, _ptr(buf), C.byref(lmax), off, self.stream), 'ra_texture_mips')
+        return [buf[:, off[l]:off[l + 1]].reshape(Bt, TH >> l, TW >> l, Cn) for l in range(lmax.value + 1)]
+
+    def _texture_args(self, who, tex, uv, uv_da, filter_mode, boundary_mode, max_mip_level):
+        d = self.device
+        t, q = _f32(tex, d), _f32(uv, d)
+        t = t[None] if t.ndim == 3 else t
+        if filter_mode == 'auto':
+            filter_mode = 'linear-mipmap-linear' if uv_da is not None else 'linear'
+        if filter_mode not in _lib.RA_TEX_FILTERS or boundary_mode not in _lib.RA_TEX_BOUNDARIES:
+            raise NotImplementedError(f'{who}: filter_mode {filter_mode!r} / boundary_mode {boundary_mode!r} is not supported '
+                                      f'({sorted(_lib.RA_TEX_FILTERS)} and {sorted(_lib.RA_TEX_BOUNDARIES)} are)')
+        if t.ndim != 4 or q.ndim != 4 or q.shape[3] != 2 or t.shape[0] not in (1, q.shape[0]):
+            raise ValueError(f'{who}: tex must be (TH, TW, C), (1, TH, TW, C) or (B, TH, TW, C) and uv (B, H, W, 2)')
+        da = None
+        if filter_mode == 'linear-mipmap-linear':
+            if uv_da is None:
+                raise ValueError(f'{who}: linear-mipmap-linear needs uv_da')
+            da = _f32(uv_da, d)
+            if da.shape != q.shape[:3] + (4,):
+                raise ValueError(f'{who}: uv_da must be (B, H, W, 4)')
+        mm = _lib.RA_TEX_MAX_LEVELS - 1 if max_mip_level is None else int(max_mip_level)
+        return t, q, da, _lib.RA_TEX_FILTERS[filter_mode], _lib.RA_TEX_BOUNDARIES[boundary_mode], mm
+
+    def texture(self, tex, uv, uv_da=None, filter_mode='auto', boundary_mode='wrap', max_mip_level=None):
+        """tex (TH,TW,C), (1,TH,TW,C) shared by the views or (B,TH,TW,C), row 0 at v = 0, 1 <= C <= 64; uv (B,H,W,2); uv_da (B,H,W,4) =
+        (du/dX, du/dY, dv/dX, dv/dY) -> (B,H,W,C) float32 on the device (include/relightableavatar.h: ra_texture).
+        filter_mode 'nearest', 'linear', 'linear-mipmap-linear' or 'auto' (the last with uv_da, else 'linear'); boundary_mode 'wrap' or
+        'clamp'; max_mip_level None: as many levels as the sizes allow.  A non-finite uv gives 0.  Nothing is read back."""
+        t, q, da, flt, bnd, mm = self._texture_args('Engine.texture', tex, uv, uv_da, filter_mode, boundary_mode, max_mip_level)
+        Bt, TH, TW, Cn = t.shape
+        B, H, W = q.shape[:3]
+        out = torch.empty(B, H, W, Cn, dtype=torch.float32, device=self.device)
+        check(self.lib.ra_texture(self.ctx, _ptr(t), Bt, TH, TW, Cn, _ptr(q), _ptr(da), B, H, W, flt, bnd, mm, _ptr(out), self.stream), 'ra_texture')
+        return out
+
+    def texture_backward(self, tex, uv, dout, uv_da=None, filter_mode='auto', boundary_mode='wrap', max_mip_level=None, want=('duv', 'dtex')):
+        """the gradient of Engine.texture, first order (the texel cells, the level pair and lod held fixed; none to uv_da): dout (B,H,W,C)
+        -> dotdict(duv (B,H,W,2), dtex shaped like tex) on the device (ra_texture_backward).  No float atomics: the same bits every
+        time; row t of a per-view dtex depends on view t alone, a shared texture adds the views in ascending order.  Nothing is read
+        back."""
+        t, q, da, flt, bnd, mm = self._texture_args('Engine.texture_backward', tex, uv, uv_da, filter_mode, boundary_mode, max_mip_level)
+        g = _f32(dout, self.device)
+        Bt, TH, TW, Cn = t.shape
+        B, H, W = q.shape[:3]
+        if g.shape != (B, H, W, Cn):
+            raise ValueError(f'Engine.texture_backward: dout must be ({B}, {H}, {W}, {Cn})')
+        out = dotdict()
+        if 'duv' in want:
+            out.duv = torch.empty_like(q)
+        if 'dtex' in want:
+            out.dtex = torch.empty_like(t)
+        if not want:
+            return out
+        check(self.lib.ra_texture_backward(self.ctx, _ptr(t), Bt, TH, TW, Cn, _ptr(q), _ptr(da), B, H, W, flt, bnd, mm, _ptr(g), _ptr(out.get('duv')),
+                                           _ptr(out.get('dtex')), self.stream), 'ra_texture_backward')
+        if 'dtex' in out and tex.ndim == 3:
+            out.dtex = out.dtex[0]
+        return out
+
     def cloth(self, topology, rest_verts, vm, fm, material=None):
         """topology (Engine.topology), rest_verts (V,3), vm (M,2) material coordinates, fm (F,3) integers into vm, material (an
         object or dict with density, thickness, young_modulus, poisson_ratio, bending_multiplier, stretch_multiplier and optionally

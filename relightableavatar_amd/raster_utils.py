@@ -1,11 +1,19 @@
-"""The reference's lib/utils/raster_utils.py on the device rasteriser (Engine.rasterize / Engine.interpolate / Engine.antialias, DESIGN.md
-sections 25 and 26).
+"""The reference's lib/utils/raster_utils.py on the device rasteriser (Engine.rasterize / Engine.interpolate / Engine.antialias /
+Engine.texture, DESIGN.md sections 25, 26 and 27).
 
-The camera helpers are the reference's torch arithmetic.  `rasterize`, `interpolate` and `antialias` are autograd ops over the HIP
-kernels, first order only, in nvdiffrast's layouts and argument order.  `render_nvdiffrast` is the reference's ATTRIBUTE path.
+The camera helpers are the reference's torch arithmetic.  `rasterize`, `interpolate`, `antialias` and `texture` are autograd ops over the
+HIP kernels, first order only, in nvdiffrast's layouts and argument order.  `render_nvdiffrast` is the reference's ATTRIBUTE path and
+`render_textured` its two TEXTURE branches (uv + img, with or without attributes).
 
-Deliberate limits (DESIGN.md sections 6, 25 and 26):
-  * the texture path (uv / img, dr.texture, mip maps, rast_db) raises NotImplementedError;
+The texture path has names of its own, because the older calls keep their signatures, values and refusals: `rasterize_db` returns
+(rast, rast_db), `interpolate_db` returns (out, out_da), `texture` is nvdiffrast's dr.texture, `render_textured` the reference's call
+with uv / img.  `interpolate(rast_db=)` and `render_nvdiffrast(uv=, img=)` still raise NotImplementedError and name these.
+
+Deliberate limits (DESIGN.md sections 6, 25, 26 and 27):
+  * `texture` is this project's statement of the published algorithm (Laine et al. 2020, section 3.3; csrc/ra_texture_rules.hpp): first
+    order with the texel cells, the level pair and the level of detail held fixed, so uv_da and rast_db carry no gradient (nvdiffrast
+    differentiates lod); filter modes nearest, linear, linear-mipmap-linear and auto, boundary modes wrap and clamp;
+    linear-mipmap-nearest, mip_level_bias, a prebuilt mip, and the boundary modes zero and cube raise NotImplementedError;
   * `antialias` is this project's statement of the published algorithm (Laine et al. 2020, section 3.4; csrc/ra_antialias_rules.hpp), not
     a reproduction of nvdiffrast's output: no fixed-point snapping, and only the own pixel's face is searched for silhouette edges, as
     in the paper.  render_nvdiffrast applies it only with antialias=True (the reference's behaviour); by default it skips that step, the
@@ -166,6 +174,26 @@ class _Antialias(torch.autograd.Function):
         return dcolor, None, dpos, None, None, None, None
 
 
+class _Texture(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tex, uv, uv_da, filter_mode, boundary_mode, max_mip_level, engine):
+        out = engine.texture(tex, uv, uv_da, filter_mode, boundary_mode, max_mip_level)
+        ctx.save_for_backward(tex.detach(), uv.detach(), None if uv_da is None else uv_da.detach())
+        ctx.engine, ctx.modes = engine, (filter_mode, boundary_mode, max_mip_level)
+        ctx.like = (tex.dtype, tex.device, uv.dtype, uv.device)
+        return out.to(device=uv.device)
+
+    @staticmethod
+    def backward(ctx, g):
+        tex, uv, uv_da = ctx.saved_tensors
+        want = tuple(k for k, need in zip(('dtex', 'duv'), ctx.needs_input_grad[:2]) if need)
+        t_dtype, t_device, u_dtype, u_device = ctx.like
+        d = ctx.engine.texture_backward(tex, uv, g, uv_da, *ctx.modes, want=want) if want else dotdict()
+        dtex = d.dtex.reshape(tex.shape).to(device=t_device, dtype=t_dtype) if 'dtex' in d else None
+        duv = d.duv.to(device=u_device, dtype=u_dtype) if 'duv' in d else None
+        return dtex, duv, None, None, None, None, None            # uv_da carries no gradient (first order: lod held fixed)
+
+
 def rasterize(pos: torch.Tensor, faces: torch.Tensor, H: int, W: int, engine=None, topology=None) -> torch.Tensor:
     """pos (B,V,4) clip-space positions, faces (F,3) -> nvdiffrast's (B,H,W,4) float32 on the device: u, v, z/w, face + 1 (0 where the
     pixel is empty).  Differentiable in pos through u and v with the face map held fixed (first order); z/w and the face carry no
@@ -177,9 +205,11 @@ def rasterize(pos: torch.Tensor, faces: torch.Tensor, H: int, W: int, engine=Non
 
 def interpolate(attrs: torch.Tensor, rast: torch.Tensor, faces: torch.Tensor, rast_db=None, diff_attrs=None, engine=None, topology=None) -> torch.Tensor:
     """attrs (V,A) or (B,V,A), 1 <= A <= 64; rast: rasterize's output -> (B,H,W,A) float32, 0 where the pixel is empty.  Differentiable
-    in attrs and in rast's u, v (first order).  rast_db / diff_attrs (pixel differentials) are not supported."""
+    in attrs and in rast's u, v (first order).  rast_db / diff_attrs (pixel differentials) raise NotImplementedError here: interpolate_db
+    takes them."""
     if rast_db is not None or diff_attrs is not None:
-        raise NotImplementedError('interpolate: pixel differentials (rast_db, diff_attrs) belong to the texture path, which is not supported')
+        raise NotImplementedError('interpolate: pixel differentials (rast_db, diff_attrs) are returned by interpolate_db, which has its own name '
+                                  'because this call returns one tensor')
     return _Interpolate.apply(attrs, rast, faces, _engine(engine), topology)
 
 
@@ -195,6 +225,58 @@ def antialias(color: torch.Tensor, rast: torch.Tensor, pos: torch.Tensor, tri: t
     return _Antialias.apply(color, rast, pos, tri, float(pos_gradient_boost), _engine(engine), topology)
 
 
+def _to_clip(verts, R, T, K, H, W):
+    """the reference's model-view-projection step: verts (B,V,3|4) float32 -> clip-space (B,V,4)"""
+    if R is not None and T is not None:
+        vverts = verts @ R.mT + T.mT
+        homovverts = torch.cat([vverts, vverts.new_ones((*vverts.shape[:-1], 1))], dim=-1)
+    elif verts.shape[-1] == 3:
+        homovverts = torch.cat([verts, verts.new_ones((*verts.shape[:-1], 1))], dim=-1)
+    else:
+        homovverts = verts
+    if K is None:
+        K = get_ndc_perspective_matrix(torch.tensor([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, -2 * 0.001], [0, 0, 1, 0]], device=verts.device, dtype=verts.dtype), H, W)
+    return homovverts @ K.mT
+
+
+def rasterize_db(pos: torch.Tensor, faces: torch.Tensor, H: int, W: int, engine=None, topology=None):
+    """`rasterize` with nvdiffrast's second output: -> (rast, rast_db).  rast has rasterize's bits and rasterize's backward; rast_db
+    (B,H,W,4) = (du/dX, du/dY, dv/dX, dv/dY), the pixel differentials of the barycentrics, 0 where the pixel is empty, detached."""
+    rast = rasterize(pos, faces, H, W, engine=engine, topology=topology)
+    return rast, _engine(engine).raster_db(pos, faces, _split(rast))
+
+
+def interpolate_db(attrs: torch.Tensor, rast: torch.Tensor, faces: torch.Tensor, rast_db: torch.Tensor, diff_attrs, engine=None, topology=None):
+    """`interpolate` with pixel differentials: rast_db: rasterize_db's, diff_attrs: a list of channels of attrs or 'all' (at most 64)
+    -> (out, out_da).  out has interpolate's bits and interpolate's backward; out_da (B,H,W,2n) = (da_0/dX, da_0/dY, da_1/dX, ...)
+    in the order of diff_attrs, nvdiffrast's layout, detached."""
+    channels = list(range(attrs.shape[-1])) if isinstance(diff_attrs, str) and diff_attrs == 'all' else [int(c) for c in diff_attrs]
+    out = _Interpolate.apply(attrs, rast, faces, _engine(engine), topology)
+    return out, _engine(engine).interpolate_da(attrs, _split(rast), faces, rast_db, channels)
+
+
+def texture(tex: torch.Tensor, uv: torch.Tensor, uv_da: torch.Tensor = None, mip_level_bias=None, mip=None, filter_mode: str = 'auto',
+            boundary_mode: str = 'wrap', max_mip_level: int = None, engine=None) -> torch.Tensor:
+    """nvdiffrast's texture, in its argument order: tex (1,TH,TW,C) shared by the views or (B,TH,TW,C), row 0 at v = 0; uv (B,H,W,2);
+    uv_da (B,H,W,4): interpolate_db's out_da of the two uv channels -> (B,H,W,C) float32 (module docstring).
+    filter_mode 'auto' is 'linear-mipmap-linear' with uv_da and 'linear' without.  Differentiable in tex and uv, first order: the texel
+    cells, the level pair and the level of detail are held fixed and uv_da carries no gradient.  mip_level_bias, mip, 'linear-mipmap-nearest'
+    and the boundary modes 'zero' and 'cube' raise NotImplementedError."""
+    if mip_level_bias is not None or mip is not None:
+        raise NotImplementedError('texture: mip_level_bias and a prebuilt mip are not supported')
+    if filter_mode == 'auto':
+        filter_mode = 'linear-mipmap-linear' if uv_da is not None else 'linear'
+    if filter_mode not in ('nearest', 'linear', 'linear-mipmap-linear'):
+        raise NotImplementedError(f'texture: filter_mode {filter_mode!r} is not supported (nearest, linear, linear-mipmap-linear and auto are)')
+    if boundary_mode not in ('wrap', 'clamp'):
+        raise NotImplementedError(f'texture: boundary_mode {boundary_mode!r} is not supported (wrap and clamp are)')
+    if tex.ndim != 4 or uv.ndim != 4:
+        raise ValueError('texture: tex must be (1 or B, TH, TW, C) and uv (B, H, W, 2)')
+    if filter_mode != 'linear-mipmap-linear':
+        uv_da = None
+    return _Texture.apply(tex, uv, uv_da, filter_mode, boundary_mode, max_mip_level, _engine(engine))
+
+
 def render_nvdiffrast(verts: torch.Tensor, faces: torch.Tensor, attrs: torch.Tensor = None, uv: torch.Tensor = None, img: torch.Tensor = None,
                       H: int = 512, W: int = 512, R: torch.Tensor = None, T: torch.Tensor = None, K: torch.Tensor = None, R_S: int = 2,
                       pos_gradient_boost: float = 1.0, engine=None, topology=None, antialias: bool = False):
@@ -204,9 +286,10 @@ def render_nvdiffrast(verts: torch.Tensor, faces: torch.Tensor, attrs: torch.Ten
     antialias=True is the REFERENCE'S behaviour: `antialias` (this module) is applied to cat([attributes, mask]) before the resize with
     pos_gradient_boost, so the mask is fractional along the outline and carries a gradient to verts.  The default False skips that step
     (the values this call returned before the op existed): the mask is soft through R_S alone, carries no gradient, and
-    pos_gradient_boost is unused.  uv / img (the texture path) raise NotImplementedError."""
+    pos_gradient_boost is unused.  uv / img (the texture path) raise NotImplementedError here: render_textured takes them."""
     if uv is not None or img is not None:
-        raise NotImplementedError('render_nvdiffrast: the texture path (uv, img: dr.texture, mip maps, rast_db) is not supported')
+        raise NotImplementedError('render_nvdiffrast: the texture path (uv, img) is render_textured, which has its own name because it returns '
+                                  'the image as well')
     assert attrs is not None
     assert int(R_S) == R_S
     if verts.ndim == 2 and R is not None:
@@ -217,16 +300,7 @@ def render_nvdiffrast(verts: torch.Tensor, faces: torch.Tensor, attrs: torch.Ten
     attrs = attrs.float().contiguous()
     faces = faces.int().contiguous()
     A = attrs.shape[-1]
-    if R is not None and T is not None:
-        vverts = verts @ R.mT + T.mT
-        homovverts = torch.cat([vverts, vverts.new_ones((*vverts.shape[:-1], 1))], dim=-1)
-    elif verts.shape[-1] == 3:
-        homovverts = torch.cat([verts, verts.new_ones((*verts.shape[:-1], 1))], dim=-1)
-    else:
-        homovverts = verts
-    if K is None:
-        K = get_ndc_perspective_matrix(torch.tensor([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, -2 * 0.001], [0, 0, 1, 0]], device=verts.device, dtype=verts.dtype), H, W)
-    ndcverts = homovverts @ K.mT
+    ndcverts = _to_clip(verts, R, T, K, H, W)
     R_S = int(R_S)
     R_H, R_W = int(H * R_S), int(W * R_S)
     rast = rasterize(ndcverts, faces, R_H, R_W, engine=engine, topology=topology)
@@ -238,3 +312,53 @@ def render_nvdiffrast(verts: torch.Tensor, faces: torch.Tensor, attrs: torch.Ten
     aa = bilinear_interpolation(aa, [H, W])
     rast_attrs, rast_msk = aa.split([A, 1], dim=-1)
     return rast_attrs, rast_msk[..., 0]
+
+
+def render_textured(verts: torch.Tensor, faces: torch.Tensor, attrs: torch.Tensor = None, uv: torch.Tensor = None, img: torch.Tensor = None,
+                    H: int = 512, W: int = 512, R: torch.Tensor = None, T: torch.Tensor = None, K: torch.Tensor = None, R_S: int = 2,
+                    pos_gradient_boost: float = 1.0, engine=None, topology=None, antialias: bool = False):
+    """The reference's render_nvdiffrast, its two TEXTURE branches: uv (B,V,2) or (V,2) per-vertex texture coordinates, img (B,TH,TW,C)
+    or (1,TH,TW,C) with the image's top row first (it is flipped, as the reference does, so that v = 0 is the bottom row); the other
+    arguments as render_nvdiffrast -> (rast_attrs (B,H,W,A), rast_img (B,H,W,C), rast_msk (B,H,W)) with attrs, (rast_img, rast_msk)
+    without.  The colour is `texture(img.flip(1), puv, puv_da, max_mip_level=8)` with puv_da the pixel differentials of uv, zeroed
+    outside the mask, concatenated with the attributes and the mask, optionally antialiased (antialias=True is the reference's
+    behaviour, the default False matches render_nvdiffrast here) and resized bilinearly.  The texture-only call works here; the
+    reference's dies on attrs.ndim before it draws."""
+    assert uv is not None and img is not None
+    assert int(R_S) == R_S
+    if verts.ndim == 2 and R is not None:
+        verts = verts[None].expand(R.shape[0], *verts.shape)
+    verts = verts.float().contiguous()
+    B = verts.shape[0]
+    if uv.ndim == 2:
+        uv = uv[None].expand(B, *uv.shape)
+    if attrs is not None and attrs.ndim == 2:
+        attrs = attrs[None].expand(B, *attrs.shape)
+    uv = uv.float().contiguous()
+    faces = faces.int().contiguous()
+    ndcverts = _to_clip(verts, R, T, K, H, W)
+    R_S = int(R_S)
+    R_H, R_W = int(H * R_S), int(W * R_S)
+    rast, rast_db = rasterize_db(ndcverts, faces, R_H, R_W, engine=engine, topology=topology)
+    rend_msk = rast[:, :, :, 3] != 0
+    if attrs is not None:
+        A = attrs.shape[-1]
+        interp, puv_da = interpolate_db(torch.cat([attrs.float(), uv], dim=-1).contiguous(), rast, faces, rast_db, [A, A + 1], engine=engine, topology=topology)
+        pattrs, puv = interp.split([A, 2], dim=-1)
+    else:
+        puv, puv_da = interpolate_db(uv, rast, faces, rast_db, [0, 1], engine=engine, topology=topology)
+    # an empty pixel gets a NaN uv: texture returns 0 there — the reference zeroes the rgb outside the mask — and its backward spends
+    # nothing on it (interpolate's 0 would send every empty pixel's taps to the texels around uv = (0, 0): one long run per texel)
+    puv = torch.where(rend_msk[..., None], puv, torch.full_like(puv, float('nan')))
+    prgb = texture(img.float().flip(1), puv.contiguous(), puv_da.contiguous(), max_mip_level=8, engine=engine)
+    msk = rend_msk.view(B, R_H, R_W, 1).to(prgb.dtype)
+    aa = torch.cat([pattrs, prgb, msk] if attrs is not None else [prgb, msk], dim=-1)
+    if antialias:
+        aa = _Antialias.apply(aa, rast, ndcverts, faces, float(pos_gradient_boost), _engine(engine), topology)
+    aa = bilinear_interpolation(aa, [H, W])
+    Cn = prgb.shape[-1]
+    if attrs is not None:
+        rast_attrs, rast_img, rast_msk = aa.split([A, Cn, 1], dim=-1)
+        return rast_attrs, rast_img, rast_msk[..., 0]
+    rast_img, rast_msk = aa.split([Cn, 1], dim=-1)
+    return rast_img, rast_msk[..., 0]
