@@ -1076,6 +1076,28 @@ int ra_sdf_volume(ra_ctx* ctx, const float* xs_dev, int nx, const float* ys_dev,
                   void* stream);
 int ra_marching_cubes(ra_ctx* ctx, const float* volume_dev, int nx, int ny, int nz, float iso, float* verts_dev, int* faces_dev,
                       int* n_verts, int* n_faces, void* stream);
+/* The backward of ra_marching_cubes and grid attributes carried to its vertices (csrc/ra_mcubes_grad_rules.hpp).
+ * A crossed edge owned by grid point p along `axis`, q its other end, a = vol[p], b = vol[q], v its vertex index (the forward's):
+ *   d = b - a, t = (iso - a) / d — the forward's own bits;
+ *   attribute forward: attr[v][c] = (1 - t) A[p][c] + t A[q][c], two products and one add;
+ *   gt = dverts[v][axis] (+0 without dverts), then gt += dattr[v][c] * (A[q][c] - A[p][c]) for c ascending; s = gt / d;
+ *   dvolume[p] += (t - 1) s, dvolume[q] += -(t s); dA[p][c] += (1 - t) dattr[v][c], dA[q][c] += t dattr[v][c].
+ * Every step is one rounded fp32 operation.  A grid point adds its terms from +0 in a fixed order — its own edges towards +x, +y, +z,
+ * then the edges arriving from -x, -y, -z — as a gather: no float atomics, the same bits on every run.  The set of crossed edges is
+ * held fixed (no d / d iso, no second order).  An edge with a non-finite end contributes nothing to either end.
+ * attrs_dev: DEVICE n x C fp32 (n = nx ny nz grid points, x slowest), 0 <= C <= 64.
+ * ra_marching_cubes_attrs writes out_dev (n_verts x C) in the forward's vertex order.
+ * ra_marching_cubes_backward: dverts_dev n_verts x 3 or NULL, dattr_dev n_verts x C (C == 0: attrs / dattr are not read), dvolume_dev n or
+ * NULL, dattrs_grid_dev n x C or NULL (one of the two at least); every output is written in full, zeros included.
+ * Both are asynchronous and make NO read-back: they classify and sum the volume they are given again, in scratch of their own (a
+ * pending size query of ra_marching_cubes stays valid), and bound every vertex access by n_verts — a volume that changed since the
+ * forward gives a wrong result, never an access outside the arrays.  n_verts == 0: the outputs are zero-filled, nothing else runs.
+ * Errors, before the ctx is touched: "null argument", "bad sizes" (an axis below 2, more than 2^27 points, C outside 0..64, n C,
+ * 3 n_verts or n_verts C not below 2^31), "bad iso". */
+int ra_marching_cubes_attrs(ra_ctx* ctx, const float* volume_dev, int nx, int ny, int nz, float iso, const float* attrs_dev, int C, int n_verts,
+                            float* out_dev, void* stream);
+int ra_marching_cubes_backward(ra_ctx* ctx, const float* volume_dev, int nx, int ny, int nz, float iso, const float* dverts_dev, int n_verts,
+                               const float* attrs_dev, const float* dattr_dev, int C, float* dvolume_dev, float* dattrs_grid_dev, void* stream);
 /* The largest component of a triangle mesh, components being sets of faces connected through SHARED EDGES (two faces that only share
  * a vertex are not connected) — trimesh's split(only_watertight=False) followed by "the one with the most vertices".  Size = the
  * number of distinct vertices the component's faces refer to; among equals the component that holds the lowest face index wins.  The

@@ -239,6 +239,9 @@ SYMBOLS = {
                                 C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     'ra_marching_cubes': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                     C.POINTER(C.c_int), C.c_void_p]),
+    'ra_marching_cubes_attrs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'ra_marching_cubes_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     'ra_mesh_largest_component': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.c_void_p]),
     'ra_mcubes_tile': (C.c_int, [C.c_int]),

@@ -3,6 +3,7 @@
 // or two; the render hot path is ra_api.cpp.
 #include "ra_api_impl.hpp"
 #include "ra_mcubes.hpp"
+#include "ra_mcubes_grad_rules.hpp"
 #include "ra_topo_rules.hpp"
 #include "ra_fit_rules.hpp"
 #include "ra_cloth_rules.hpp"
@@ -1588,15 +1589,16 @@ int ra_mesh_extract_stats(const ra_ctx* c, int which) {
     return !c ? -1 : which == 0 ? c->vol_readbacks : which == 1 ? c->mc_query.readbacks : which == 2 ? c->lcc_query.readbacks : which == 3 ? c->lcc_query.passes : 0;
 }
 
-static int mc_job(ra_ctx* c, const float* vol, int nx, int ny, int nz, float iso, McJob* j) {
+// pre: "mc_" the forward's scratch, which holds a pending size query's offsets; "mcg_" that of the backward and the vertex attributes
+static int mc_job(ra_ctx* c, const float* vol, int nx, int ny, int nz, float iso, McJob* j, const std::string& pre = "mc_") {
     const size_t n = (size_t)nx * ny * nz;
     int err = 0;
     j->vol = vol; j->nx = nx; j->ny = ny; j->nz = nz; j->iso = iso;
     j->temp_bytes = mc_scan_temp_bytes((int)n + 1);
-    j->cnt = c->buf<unsigned long long>("mc_cnt", n + 1, &err);
-    j->off = c->buf<unsigned long long>("mc_off", n + 1, &err);
-    j->mask = c->buf<unsigned char>("mc_mask", n, &err);
-    j->temp = c->buf<char>("mc_tmp", j->temp_bytes + 16, &err);
+    j->cnt = c->buf<unsigned long long>(pre + "cnt", n + 1, &err);
+    j->off = c->buf<unsigned long long>(pre + "off", n + 1, &err);
+    j->mask = c->buf<unsigned char>(pre + "mask", n, &err);
+    j->temp = c->buf<char>(pre + "tmp", j->temp_bytes + 16, &err);
     return err;
 }
 
@@ -1676,6 +1678,55 @@ int ra_marching_cubes(ra_ctx* c, const float* volume, int nx, int ny, int nz, fl
     if (q.n_verts == 0) return 0;   // no crossing: no vertex, no face
     RA_CHECK(!mc_job(c, volume, nx, ny, nz, iso, &j), "ra_marching_cubes: out of device memory");      // the buffers of the query: nothing grows
     launch_mc_emit(j, verts, q.n_verts, faces, q.n_faces, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+static bool mcg_sizes_ok(int nx, int ny, int nz, int C, int n_verts) {
+    if (nx < 2 || ny < 2 || nz < 2 || (long long)nx * ny * nz > MC_MAX_POINTS || C < 0 || C > MCG_MAX_C || n_verts < 0) return false;
+    const long long lim = 1ll << 31, n = (long long)nx * ny * nz;
+    return n * (C > 0 ? C : 1) < lim && (long long)n_verts * (C > 3 ? C : 3) < lim;
+}
+
+int ra_marching_cubes_attrs(ra_ctx* c, const float* volume, int nx, int ny, int nz, float iso, const float* attrs, int C, int n_verts, float* out,
+                            void* stream) {
+    RA_CHECK(c && volume, "ra_marching_cubes_attrs: null argument");
+    RA_CHECK(mcg_sizes_ok(nx, ny, nz, C, n_verts),
+             "ra_marching_cubes_attrs: bad sizes (2 per axis at least, 2^27 points at most, 0 <= C <= 64, element counts below 2^31)");
+    RA_CHECK(iso == iso, "ra_marching_cubes_attrs: bad iso (NaN)");
+    RA_CHECK(C == 0 || n_verts == 0 || (attrs && out), "ra_marching_cubes_attrs: null argument (attrs, out)");
+    if (C == 0 || n_verts == 0) return 0;       // nothing to write
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    McJob j{};
+    RA_CHECK(!mc_job(c, volume, nx, ny, nz, iso, &j, "mcg_"), "ra_marching_cubes_attrs: out of device memory");
+    RA_CHECK(launch_mc_count(j, s) == 0, "ra_marching_cubes_attrs: device scan failed");
+    launch_mcg_attrs(j, attrs, C, n_verts, out, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_marching_cubes_backward(ra_ctx* c, const float* volume, int nx, int ny, int nz, float iso, const float* dverts, int n_verts, const float* attrs,
+                               const float* dattr, int C, float* dvolume, float* dattrs_grid, void* stream) {
+    RA_CHECK(c && volume && (dvolume || dattrs_grid), "ra_marching_cubes_backward: null argument");
+    RA_CHECK(mcg_sizes_ok(nx, ny, nz, C, n_verts),
+             "ra_marching_cubes_backward: bad sizes (2 per axis at least, 2^27 points at most, 0 <= C <= 64, element counts below 2^31)");
+    RA_CHECK(iso == iso, "ra_marching_cubes_backward: bad iso (NaN)");
+    RA_CHECK(C == 0 || n_verts == 0 || (attrs && dattr), "ra_marching_cubes_backward: null argument (attrs, dattr)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    const size_t n = (size_t)nx * ny * nz;
+    if (C == 0) dattrs_grid = nullptr;          // n x 0: nothing to write
+    if (n_verts == 0) {                         // no vertex: the outputs are zeros, nothing else runs
+        if (dvolume) RA_HIP(hipMemsetAsync(dvolume, 0, n * sizeof(float), s));
+        if (dattrs_grid) RA_HIP(hipMemsetAsync(dattrs_grid, 0, n * C * sizeof(float), s));
+        return 0;
+    }
+    if (!dvolume && !dattrs_grid) return 0;
+    McJob j{};
+    RA_CHECK(!mc_job(c, volume, nx, ny, nz, iso, &j, "mcg_"), "ra_marching_cubes_backward: out of device memory");
+    RA_CHECK(launch_mc_count(j, s) == 0, "ra_marching_cubes_backward: device scan failed");
+    launch_mcg_backward(j, dverts, n_verts, attrs, dattr, C, dvolume, dattrs_grid, s);
     RA_HIP(hipGetLastError());
     return 0;
 }

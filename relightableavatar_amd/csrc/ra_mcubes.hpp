@@ -54,6 +54,11 @@ size_t mc_scan_temp_bytes(int n);
 size_t lcc_sort_temp_bytes(int n);
 int launch_mc_count(const McJob& j, hipStream_t s);
 void launch_mc_emit(const McJob& j, float* verts, int n_verts, int* faces, int n_faces, hipStream_t s);
+// The backward of marching cubes and its vertex attributes (ra_mcubes_grad.hip), behind launch_mc_count on a McJob whose buffers are the
+// backward's own, so that a pending size query of the forward keeps its offsets
+void launch_mcg_attrs(const McJob& j, const float* attrs, int C, int n_verts, float* out, hipStream_t s);
+void launch_mcg_backward(const McJob& j, const float* dverts, int n_verts, const float* attrs, const float* dattr, int C, float* dvolume, float* dattrs_grid,
+                         hipStream_t s);
 int launch_lcc_links(const LccJob& j, hipStream_t s);
 void launch_lcc_passes(const LccJob& j, hipStream_t s);
 int launch_lcc_select(const LccJob& j, hipStream_t s);

@@ -1289,6 +1289,62 @@ class Engine:
             check(self.lib.ra_marching_cubes(self.ctx, _ptr(vol), nx, ny, nz, float(iso), _ptr(verts), _ptr(faces), None, None, self.stream), 'ra_marching_cubes')
         return verts, faces
 
+    def _mc_volume(self, volume, attrs, who):
+        if volume.ndim != 3 or min(volume.shape) < 2:
+            raise ValueError(f'{who}: volume must be (nx, ny, nz) with at least 2 points per axis')
+        vol = _f32(volume, self.device)
+        if attrs is not None:
+            if attrs.numel() % vol.numel() or attrs.shape[0] not in (vol.shape[0], vol.numel()):
+                raise ValueError(f'{who}: attrs must be (nx, ny, nz, C) or (nx * ny * nz, C)')
+            attrs = _f32(attrs, self.device).reshape(vol.numel(), -1)
+        return vol, attrs
+
+    def marching_cubes_attrs(self, volume, iso, attrs, n_verts):
+        """grid attributes (nx,ny,nz,C) or (n,C) carried to the n_verts vertices of Engine.marching_cubes(volume, iso), in its vertex
+        order: (n_verts, C) float32, (1 - t) A[p] + t A[q] along each crossed edge (include/relightableavatar.h:
+        ra_marching_cubes_attrs).  Asynchronous: no read-back."""
+        vol, A = self._mc_volume(volume, attrs, 'marching_cubes_attrs')
+        nx, ny, nz = (int(v) for v in vol.shape)
+        out = torch.empty(int(n_verts), A.shape[1], dtype=torch.float32, device=self.device)
+        check(self.lib.ra_marching_cubes_attrs(self.ctx, _ptr(vol), nx, ny, nz, float(iso), _ptr(A), A.shape[1], int(n_verts), _ptr(out), self.stream),
+              'ra_marching_cubes_attrs')
+        return out
+
+    def marching_cubes_backward(self, volume, iso, n_verts, dverts=None, attrs=None, dattr=None, want=('dvolume', 'dattrs')):
+        """the backward of Engine.marching_cubes / marching_cubes_attrs at fixed topology (ra_marching_cubes_backward): dverts (n_verts,3)
+        and / or dattr (n_verts,C) with the grid attributes -> dotdict(dvolume (nx,ny,nz), dattrs in attrs' shape), those of `want`
+        ('dattrs' needs attrs).  A gather over the grid points: bit-reproducible, asynchronous, no read-back."""
+        unknown = set(want) - {'dvolume', 'dattrs'}
+        if unknown or not want:
+            raise ValueError(f"marching_cubes_backward: want must name 'dvolume' and / or 'dattrs', got {tuple(want)}")
+        if (attrs is None) != (dattr is None):
+            raise ValueError('marching_cubes_backward: attrs and dattr go together')
+        if 'dattrs' in want and attrs is None and tuple(want) != ('dvolume', 'dattrs'):
+            raise ValueError("marching_cubes_backward: 'dattrs' needs attrs and dattr")
+        vol, A = self._mc_volume(volume, attrs, 'marching_cubes_backward')
+        nx, ny, nz = (int(v) for v in vol.shape)
+        d, n_verts = self.device, int(n_verts)
+        Cn = A.shape[1] if A is not None else 0
+        if dverts is not None:
+            dverts = _f32(dverts, d)
+            if tuple(dverts.shape) != (n_verts, 3):
+                raise ValueError('marching_cubes_backward: dverts must be (n_verts, 3)')
+        if dattr is not None:
+            dattr = _f32(dattr, d)
+            if tuple(dattr.shape) != (n_verts, Cn):
+                raise ValueError('marching_cubes_backward: dattr must be (n_verts, C)')
+        out = dotdict()
+        if 'dvolume' in want:
+            out.dvolume = torch.empty_like(vol)
+        if 'dattrs' in want and A is not None:
+            out.dattrs = torch.empty(attrs.shape, dtype=torch.float32, device=d)
+        if 'dvolume' not in out and not Cn:      # nothing to write
+            return out
+        check(self.lib.ra_marching_cubes_backward(self.ctx, _ptr(vol), nx, ny, nz, float(iso), _ptr(dverts) if n_verts else None, n_verts,
+                                                  _ptr(A), _ptr(dattr) if n_verts else None, Cn, _ptr(out.get('dvolume')),
+                                                  _ptr(out.get('dattrs')) if Cn else None, self.stream), 'ra_marching_cubes_backward')
+        return out
+
     def largest_component(self, verts, faces):
         """verts (V,3) float, faces (F,3) integer -> (verts, faces) of the largest component of faces connected through shared edges, on
         the device: the most vertices, then the lowest face index; referenced vertices and faces in their original order

@@ -27,6 +27,8 @@
     icp_loss(v, t, n0, n1, dist_th, angle_th)                         :265-291 (Mesh.icp_residual: ra_icp_residual)
     bidirectional_icp_fitting(v0, f0, v1, f1, ...)                    :294-379 (relightableavatar_amd.largesteps)
     isosurface_fitting(src_verts, src_faces, tar_verts, tar_faces, ...)   :1018-1058 (Mesh.winding_grad: ra_mesh_winding_grad)
+    marching_cubes(volume, iso, attrs=None)                           an autograd op in volume and attrs (ra_marching_cubes_backward, _attrs)
+    differentiable_marching_cubes(points, decoder, chunk_size, gradient=)   :70-127 (RegisterSDFGradient: 'normal'; the exact one: 'grid')
 
 The distance and winding functions take the engine that owns the HIP context (engine=, default: evaluators.mesh_evaluator.Evaluator.engine); they
 have no CPU fallback.  sample_blend_K_closest_points, sample_closest_points, the grid helpers, sample_surface and load_obj are plain torch / text and run anywhere.  Batches: the reference's signatures carry a
@@ -718,3 +720,122 @@ def isosurface_fitting(src_verts: torch.Tensor, src_faces: torch.Tensor, tar_ver
     finally:
         target.close()
     return M.solve(param.detach(), x0=verts)
+
+
+class _MarchingCubes(torch.autograd.Function):
+    """Engine.marching_cubes and marching_cubes_attrs forwards; Engine.marching_cubes_backward at fixed topology backwards"""
+
+    @staticmethod
+    def forward(ctx, volume, attrs, iso, eng):
+        verts, faces = eng.marching_cubes(volume, iso)
+        vattrs = None if attrs is None else eng.marching_cubes_attrs(volume, iso, attrs, verts.shape[0])
+        ctx.save_for_backward(volume.detach(), None if attrs is None else attrs.detach())
+        ctx.eng, ctx.iso, ctx.n_verts = eng, iso, verts.shape[0]
+        ctx.like = [(t.device, t.dtype) if t is not None else None for t in (volume, attrs)]
+        ctx.mark_non_differentiable(faces)
+        return (verts, faces) if attrs is None else (verts, faces, vattrs)
+
+    @staticmethod
+    def backward(ctx, dverts, _dfaces, dattr=None):
+        volume, attrs = ctx.saved_tensors
+        want = tuple(k for k, need in zip(('dvolume', 'dattrs'), ctx.needs_input_grad[:2]) if need)
+        if not want:
+            return None, None, None, None
+        if attrs is not None and dattr is None:
+            dattr = torch.zeros(ctx.n_verts, attrs.numel() // volume.numel(), device=dverts.device)
+        out = ctx.eng.marching_cubes_backward(volume, ctx.iso, ctx.n_verts, dverts=dverts, attrs=attrs, dattr=dattr, want=want)
+        back = lambda g, like: None if g is None else g.to(device=like[0], dtype=like[1])
+        return (back(out.get('dvolume'), ctx.like[0]), back(out.get('dattrs'), ctx.like[1]) if attrs is not None else None, None, None)
+
+
+def marching_cubes(volume: torch.Tensor, iso: float, attrs: torch.Tensor = None, engine=None):
+    """volume (nx,ny,nz), iso a float -> (verts (V,3) float32 in INDEX coordinates, faces (F,3) int32) on the device, or (verts, faces,
+    vattrs (V,C)) with grid attributes attrs (nx,ny,nz,C) carried to the vertices along their edges.  The forward is
+    Engine.marching_cubes' own bits and its one read-back; as an autograd op it is differentiable in volume and attrs, the set of
+    crossed edges held fixed, through Engine.marching_cubes_backward (a gather: bit-reproducible, no read-back).  Not differentiable in iso."""
+    eng = _engine(engine)
+    if attrs is not None and tuple(attrs.shape[:3]) != tuple(volume.shape):
+        raise ValueError('marching_cubes: attrs must be (nx, ny, nz, C)')
+    if not (_wants_grad(volume) or (attrs is not None and _wants_grad(attrs))):
+        verts, faces = eng.marching_cubes(volume, float(iso))
+        return (verts, faces) if attrs is None else (verts, faces, eng.marching_cubes_attrs(volume, float(iso), attrs, verts.shape[0]))
+    return _MarchingCubes.apply(volume, attrs, float(iso), eng)
+
+
+class _RegisterSDFGradient(torch.autograd.Function):
+    """lib/utils/mesh_utils.py:70-91: the identity on the vertices; backwards the decoder is evaluated again at the vertices and
+    sum(-(n . g) sdf), n = normalize(d sdf / d x) held constant, is backpropagated into the decoder's parameters"""
+
+    @staticmethod
+    def forward(ctx, verts, decoder, chunk_size):
+        ctx.save_for_backward(verts)
+        ctx.decoder, ctx.chunk_size = decoder, chunk_size
+        return verts.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        verts = ctx.saved_tensors[0].detach().requires_grad_()
+        with torch.enable_grad():
+            for i in range(0, verts.shape[0], ctx.chunk_size):
+                x = verts[i:i + ctx.chunk_size]
+                sdf = ctx.decoder(x).reshape(-1)
+                n = torch.nn.functional.normalize(torch.autograd.grad(sdf.sum(), x, retain_graph=True)[0], dim=-1).detach()
+                (-(n * grad[i:i + ctx.chunk_size]).sum(-1) * sdf).sum().backward()
+        return None, None, None
+
+
+class _RegisterGridGradient(torch.autograd.Function):
+    """the identity on the vertices; backwards the gradient goes through Engine.marching_cubes_backward to the volume = -sdf and from
+    there, by a chunked evaluation of the decoder on the grid, into the decoder's parameters"""
+
+    @staticmethod
+    def forward(ctx, verts, volume, points, scale, decoder, chunk_size, eng):
+        ctx.save_for_backward(volume, points, scale)
+        ctx.decoder, ctx.chunk_size, ctx.eng, ctx.n_verts = decoder, chunk_size, eng, verts.shape[0]
+        return verts.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        volume, points, scale = ctx.saved_tensors
+        dvolume = ctx.eng.marching_cubes_backward(volume, 0.0, ctx.n_verts, dverts=grad * scale, want=('dvolume',)).dvolume.reshape(-1)
+        with torch.enable_grad():
+            for i in range(0, points.shape[0], ctx.chunk_size):
+                sdf = ctx.decoder(points[i:i + ctx.chunk_size]).reshape(-1)
+                (-dvolume[i:i + ctx.chunk_size].to(sdf.dtype) * sdf).sum().backward()
+        return (None,) * 7
+
+
+def differentiable_marching_cubes(points: torch.Tensor, decoder, chunk_size=65536, engine=None, gradient='normal'):
+    """lib/utils/mesh_utils.py:97-127.  points (X,Y,Z,3): a regular grid; decoder: (N,3) -> (N,) or (N,1) signed distances.  The decoder
+    runs on the grid in chunks under no_grad, the volume is -sdf, iso is 0, and the result is verts * (upper - lower) / (shape - 1) +
+    lower with the vertices registered for the gradient: a loss on the returned vertices reaches the decoder's parameters through
+    .backward().  Returns (verts (V,3) float32, faces (F,3) int32) on the engine's device.  The volume never leaves the device (the
+    reference goes through the host for mcubes); the one read-back is Engine.marching_cubes' (the two counts).
+
+    gradient='normal'   the reference's RegisterSDFGradient: the decoder is evaluated again at the vertices, n = normalize(d sdf / d x),
+                        and sum(-(n . g) sdf) is backpropagated.  It moves the SURFACE along its normal and assumes |d sdf / d x| = 1.
+    gradient='grid'     the exact gradient of the vertices that were computed: Engine.marching_cubes_backward gives d loss / d volume,
+                        which is pushed through a chunked evaluation of the decoder on the grid.  It moves a VERTEX along its grid edge.
+    The two agree where g is parallel to the normal (a vertex sliding along its edge by dc / n_k has moved the surface by dc along the
+    unit normal); for a linear field of unit gradient they then agree exactly (tests/test_oracle_mcubes_grad.py).  The tangential part
+    of g, which the normal form drops, the grid form turns into motion along the edge.
+
+    Deviations that hold for the forward: vertex order, face order and winding are this library's, not mcubes' —
+    vertices by (owning grid point, axis), faces wound so that their normals point towards smaller volume values, i.e. outwards."""
+    if gradient not in ('normal', 'grid'):
+        raise ValueError("differentiable_marching_cubes: gradient must be 'normal' or 'grid'")
+    if points.ndim != 4 or points.shape[-1] != 3:
+        raise ValueError('differentiable_marching_cubes: points (X,Y,Z,3); no batch dimension')
+    eng = _engine(engine)
+    sh = points.shape
+    points = points.detach().to(eng.device).reshape(-1, 3)
+    upper, lower = points.max(dim=0, keepdim=True)[0], points.min(dim=0, keepdim=True)[0]
+    with torch.no_grad():
+        sdf = torch.cat([decoder(points[i:i + chunk_size]).detach().reshape(-1) for i in range(0, points.shape[0], chunk_size)])
+    volume = (-sdf).reshape(sh[:-1]).float().contiguous()
+    verts, faces = eng.marching_cubes(volume, 0.0)
+    scale = ((upper - lower) / (torch.tensor(sh[:-1], device=points.device) - 1)).to(verts.dtype)
+    verts = (verts * scale + lower.to(verts.dtype)).requires_grad_()
+    if gradient == 'normal':
+        return _RegisterSDFGradient.apply(verts, decoder, chunk_size), faces
+    return _RegisterGridGradient.apply(verts, volume, points, scale, decoder, chunk_size, eng), faces
