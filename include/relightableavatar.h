@@ -668,6 +668,33 @@ int ra_mesh_closest(ra_ctx* ctx, const ra_mesh* mesh, const float* pts_dev, int 
                     int* face_dev, float* bary_dev, void* stream);
 /* test hook: 0 faces per leaf, 1 leaves per group, 2 points up to which a query is never sorted — the tests take their edge sizes from it */
 int ra_mesh_tile(int which);
+/* The backward of ra_mesh_closest in the points, the mesh's vertices and per-vertex attributes (the reference's grad_points / grad_tris
+ * of point_face_dist_backward, lib/utils/sample_utils.py:198-307).  It needs no ra_mesh: it reads the forward's stored outputs and a
+ * DEVICE copy of the faces (n_faces x 3 int32) of a mesh of n_verts vertices.
+ * Per row i (ra_mesh_grad_rules.hpp, every operation a named fp32 operation): p = pts[i], q = closest[i], f = face[i], b = bary[i],
+ * g = g_d2[i] the upstream gradient of d2 — the SQUARED distance —, ga = g_attr[i] (C values, 0 <= C <= 64) the upstream gradient of C
+ * attribute channels interpolated at the closest point, sum_k b[k] attr[faces[f][k]].  With the face and the barycentrics held fixed
+ * d(d2)/dp = 2 (p - q) and d(d2)/dv_k = -2 b[k] (p - q), in the face, edge and vertex regions alike.
+ * A row is LIVE when 0 <= f < n_faces and the face's three indices lie in [0, n_verts), otherwise DEAD (a non-finite point of the
+ * forward has face -1).
+ *   live:  dpts[i][c] = (2 g) * (p[c] - q[c]), one subtraction and one product; slot (i, k), k = 0..2, belongs to vertex faces[f][k]
+ *          and carries -(b[k] * dpts[i][c]) for dverts and b[k] * ga[ch] for dattr.
+ *   dead:  dpts[i] = +0 and no slot.
+ * Non-finite values of a live row are not filtered: they reach that row's dpts and its three vertices and nothing else.
+ * dverts[v] and dattr[v] are the sums of v's slots in ascending 3 i + k, taken as the run sum of ra_texture_backward: lane l of a wave
+ * adds terms l, l + 64, ... from +0 and the 64 lanes meet in the xor tree 32, 16, .., 1; a vertex without a slot gets +0.  The result
+ * is a function of the inputs in their given order, bit for bit: not of the launch shape, and not of which outputs were asked for.
+ * (The order of the rows IS the order of summation: permuting the rows keeps dpts' rows and may change dverts' last bits.)
+ * Outputs: dpts (n x 3), dverts (n_verts x 3), dattr (n_verts x C); each may be NULL, not all three.  dpts and dverts need g_d2, dattr
+ * needs g_attr.  n == 0 writes zeros to the vertex-sized outputs and reads no row pointer.
+ * Asynchronous on stream, no read-back, no float atomics: one stable radix sort of the 3 n keys (vertex, 3 i + k), one wave per
+ * vertex run.  Scratch (the keys) is allocated on the first call of a size only and belongs to the ctx: the ordering rule of the other
+ * mesh calls holds.
+ * Errors: "null argument" (no output asked for, or an output asked for without its upstream gradient), "bad sizes" (n < 0, n >= 2^30,
+ * n_verts < 1, n_faces < 1, n_faces > 2^24, C outside [0, 64]). */
+int ra_mesh_closest_backward(ra_ctx* ctx, const int* faces_dev, int n_faces, int n_verts, const float* pts_dev, const float* closest_dev,
+                             const int* face_dev, const float* bary_dev, int n, const float* g_d2_dev, const float* g_attr_dev, int C,
+                             float* dpts_dev, float* dverts_dev, float* dattr_dev, void* stream);
 /* Per point (pts: DEVICE n x 3 fp32) the generalised winding number of the mesh (Jacobson et al. 2013; the reference's winding_number,
  * lib/utils/mesh_utils.py:614-680): winding (n) = sum over every face the mesh kept of sign * Omega / (4 pi), fp32.  About 1 inside a
  * closed mesh whose faces are wound outwards, 0 outside, and a smooth value in between near holes and open boundaries; a flipped face

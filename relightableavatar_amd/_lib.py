@@ -184,6 +184,8 @@ SYMBOLS = {
     'ra_mesh_destroy': (C.c_int, [C.c_void_p, C.c_void_p]),
     'ra_mesh_closest': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'ra_mesh_tile': (C.c_int, [C.c_int]),
+    'ra_mesh_closest_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
+                                 [C.c_void_p] * 4),
     'ra_mesh_winding': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'ra_winding_tile': (C.c_int, [C.c_int]),
     'ra_mesh_winding_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

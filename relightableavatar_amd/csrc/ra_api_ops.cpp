@@ -10,6 +10,7 @@
 #include "ra_raster_rules.hpp"
 #include "ra_antialias.hpp"
 #include "ra_texture.hpp"
+#include "ra_mesh_grad.hpp"
 #include <cmath>
 #include <cstring>
 
@@ -598,6 +599,41 @@ int ra_mesh_closest(ra_ctx* c, const ra_mesh* mesh, const float* pts, int n, int
         q.perm = b.vals_sorted;
     }
     launch_mesh_closest(mesh->view, q, s);
+    RA_HIP(hipGetLastError());
+    return 0;
+}
+
+int ra_mesh_closest_backward(ra_ctx* c, const int* faces, int n_faces, int n_verts, const float* pts, const float* closest, const int* face,
+                             const float* bary, int n, const float* g_d2, const float* g_attr, int C, float* dpts, float* dverts, float* dattr,
+                             void* stream) {
+    RA_CHECK(n >= 0 && n < (1 << 30) && n_verts >= 1 && n_faces >= 1 && n_faces <= MESH_MAX_FACES && C >= 0 && C <= MESHG_MAX_C,
+             "ra_mesh_closest_backward: bad sizes (0 <= n < 2^30, n_verts >= 1, 1 <= n_faces <= 2^24, 0 <= C <= 64)");
+    RA_CHECK(c && (dpts || dverts || dattr), "ra_mesh_closest_backward: null argument (ctx, or all three outputs)");
+    // n == 0: empty arrays have no address, so no row pointer is asked for or read
+    RA_CHECK(n == 0 || ((g_d2 || !(dpts || dverts)) && (g_attr || !dattr || C == 0)),
+             "ra_mesh_closest_backward: null argument (an output without its upstream gradient)");
+    RA_CHECK(n == 0 || (faces && pts && closest && face && bary), "ra_mesh_closest_backward: null argument (faces, pts, closest, face, bary)");
+    hipStream_t s = (hipStream_t)stream;
+    RA_HIP(hipSetDevice(c->device));
+    MeshGradJob j{};
+    j.faces = faces; j.pts = pts; j.closest = closest; j.face = face; j.bary = bary; j.g_d2 = g_d2; j.g_attr = g_attr;
+    j.F = n_faces; j.V = n_verts; j.n = n; j.C = C; j.dpts = dpts; j.dverts = dverts; j.dattr = dattr;
+    MeshGradScratch t{};
+    if (n > 0 && (dverts || (dattr && C > 0))) {
+        int err = 0;
+        const size_t n_keys = 3 * (size_t)n;
+        t.sort_bytes = mesh_grad_sort_bytes((long long)n_keys);
+        t.select_bytes = mesh_grad_select_bytes((long long)n_keys);
+        t.keys = c->buf<unsigned long long>("mesh_grad_keys", n_keys, &err);
+        t.sorted = c->buf<unsigned long long>("mesh_grad_keys_sorted", n_keys, &err);
+        t.flags = c->buf<unsigned char>("mesh_grad_flags", n_keys, &err);
+        t.heads = c->buf<unsigned>("mesh_grad_heads", n_keys, &err);
+        t.count = c->buf<unsigned>("mesh_grad_count", 4, &err);
+        t.sort_temp = c->buf<char>("mesh_grad_sort_tmp", t.sort_bytes + 16, &err);
+        t.select_temp = c->buf<char>("mesh_grad_select_tmp", t.select_bytes + 16, &err);
+        RA_CHECK(!err, "ra_mesh_closest_backward: out of device memory");
+    }
+    RA_CHECK(launch_mesh_closest_backward(j, t, s) == 0, "ra_mesh_closest_backward: device sort failed");
     RA_HIP(hipGetLastError());
     return 0;
 }

@@ -77,8 +77,12 @@ class Mesh:
     collection — releases it while the engine lives; once the engine is gone the context has freed it and the handle only refuses."""
     WANT = ('d2', 'closest', 'face', 'bary')
 
-    def __init__(self, engine, handle, n_faces):
+    GRAD_WANT = ('dpts', 'dverts', 'dattr')
+
+    def __init__(self, engine, handle, n_faces, faces_dev=None, n_verts=None):
         self._engine, self._handle, self.n_faces = weakref.ref(engine), handle, n_faces
+        # (F,3) int32 and V: what closest_backward reads.  Host faces go to the device at the first backward and stay there
+        self._faces, self.n_verts = faces_dev, n_verts
 
     def _live_engine(self):
         eng = self._engine()
@@ -106,6 +110,25 @@ class Mesh:
         flags = (_lib.RA_MESH_BRUTE if brute else 0) | (0 if sort else _lib.RA_MESH_UNSORTED)
         check(eng.lib.ra_mesh_closest(eng.ctx, self._handle, _ptr(pts), n, flags, *[_ptr(out.get(k)) for k in self.WANT], eng.stream), 'ra_mesh_closest')
         return out
+
+    def faces_device(self):
+        """the mesh's (F,3) int32 faces on the engine's device; uploaded at the first call"""
+        eng = self._live_engine()
+        if self._faces is None or self.n_verts is None:
+            raise _lib.RaError('Mesh: made without its faces (build it with Engine.mesh)')
+        if self._faces.device != eng.device:
+            self._faces = self._faces.to(eng.device)
+        return self._faces
+
+    def closest_backward(self, points, out, g_d2=None, g_attr=None, want=GRAD_WANT):
+        """The backward of closest (include/relightableavatar.h: ra_mesh_closest_backward).  points (n,3); out: the dotdict closest
+        returned, with closest, face and bary; g_d2 (n,) the upstream gradient of d2, the SQUARED distance; g_attr (n,C), 0 <= C <= 64,
+        the upstream gradient of C attribute channels interpolated at the closest point -> dotdict of the wanted outputs, float32 on
+        the device: dpts (n,3), dverts (V,3), dattr (V,C).  dpts and dverts need g_d2, dattr needs g_attr; a wanted output whose
+        upstream gradient is missing is refused.  A row whose face is -1 (a non-finite point) contributes nothing and gets dpts 0.
+        No float atomics: the same inputs give the same bits, whichever outputs are asked for.  Nothing is read back."""
+        Engine.check_closest_backward_args(points, out, g_d2, g_attr, want)
+        return self._live_engine().mesh_closest_backward(self.faces_device(), self.n_verts, points, out, g_d2, g_attr, want)
 
     def winding(self, points, shape=None):
         """points (n,3) -> (n,) float32 on the device: the generalised winding number of the mesh at every point (include/
@@ -942,17 +965,75 @@ class Engine:
         check(self.lib.ra_lpips_features(self.ctx, _ptr(img), H, W, int(tap), _ptr(out), self.stream), 'ra_lpips_features')
         return out
 
-    def mesh(self, verts, faces):
+    def mesh(self, verts, faces, faces_dev=None):
         """verts (V,3) float, faces (F,3) integer -> a Mesh handle for closest-point queries (include/relightableavatar.h: ra_mesh_create).
         The vertices go to the device as they are (a device tensor makes no round trip); the faces are checked on the host against
         [0, V) before anything is launched, so faces on the device cost a read-back (and its wait) here: pass host faces where there
-        is a choice.  Otherwise asynchronous; the handle owns nothing of the caller's."""
+        is a choice.  Otherwise asynchronous; the handle owns nothing of the caller's.  The Mesh keeps the int32 faces and V for
+        Mesh.closest_backward, which reads the faces on the device: they are uploaded at the first backward, or never when faces_dev,
+        the same (F,3) int32 faces already on the engine's device, is given (a loop that rebuilds its mesh per step)."""
         verts = _f32(verts.reshape(-1, 3), self.device)
+        given = faces
         faces = faces.detach().to('cpu', torch.int32).reshape(-1, 3).contiguous()
+        if faces_dev is not None and (not torch.is_tensor(faces_dev) or faces_dev.dtype != torch.int32 or tuple(faces_dev.shape) != tuple(faces.shape)
+                                      or faces_dev.device != torch.device(self.device) or not faces_dev.is_contiguous()):
+            raise ValueError(f'Engine.mesh: faces_dev must be the contiguous int32 faces {tuple(faces.shape)} on {self.device}')
         handle = C.c_void_p()
         check(self.lib.ra_mesh_create(self.ctx, _ptr(verts), verts.shape[0], C.c_void_p(faces.data_ptr()), faces.shape[0], C.byref(handle), self.stream),
               'ra_mesh_create')
-        return Mesh(self, handle, faces.shape[0])
+        if faces_dev is None:
+            # the int32 host faces stay with the Mesh for its backward; a copy only where they are still the caller's own memory
+            keep = faces.clone() if faces.data_ptr() == given.data_ptr() else faces
+        else:
+            keep = faces_dev
+        return Mesh(self, handle, faces.shape[0], keep, verts.shape[0])
+
+    @staticmethod
+    def check_closest_backward_args(points, out, g_d2, g_attr, want):
+        """the argument errors of mesh_closest_backward, raised before any context is touched -> (want, n, C)"""
+        want = tuple(want)
+        if not want or any(k not in Mesh.GRAD_WANT for k in want):
+            raise ValueError(f'closest_backward: want must be a non-empty subset of {Mesh.GRAD_WANT}')
+        if any(k not in out for k in ('closest', 'face', 'bary')):
+            raise ValueError("closest_backward: out must hold the forward's closest, face and bary")
+        if g_d2 is None and ('dpts' in want or 'dverts' in want):
+            raise ValueError('closest_backward: dpts and dverts need g_d2')
+        if g_attr is None and 'dattr' in want:
+            raise ValueError('closest_backward: dattr needs g_attr')
+        n = points.reshape(-1, 3).shape[0]
+        if tuple(out['closest'].shape) != (n, 3) or tuple(out['bary'].shape) != (n, 3) or tuple(out['face'].shape) != (n,):
+            raise ValueError(f'closest_backward: out.closest and out.bary must be ({n}, 3) and out.face ({n},)')
+        if g_d2 is not None and g_d2.numel() != n:
+            raise ValueError(f'closest_backward: g_d2 must hold {n} values')
+        Cn = 0
+        if g_attr is not None:
+            if g_attr.ndim != 2 or g_attr.shape[0] != n or g_attr.shape[1] > 64:
+                raise ValueError(f'closest_backward: g_attr must be ({n}, C) with C <= 64')
+            Cn = g_attr.shape[1]
+        return want, n, Cn
+
+    def mesh_closest_backward(self, faces, n_verts, points, out, g_d2=None, g_attr=None, want=Mesh.GRAD_WANT):
+        """Mesh.closest_backward without a Mesh (ra_mesh_closest_backward needs none): faces (F,3) integer, n_verts, and the rest as
+        there.  Faces that are int32 on the device go in as they are."""
+        want, n, Cn = self.check_closest_backward_args(points, out, g_d2, g_attr, want)
+        d = self.device
+        faces = faces.detach().to(device=d, dtype=torch.int32).reshape(-1, 3).contiguous()
+        if faces.shape[0] < 1 or int(n_verts) < 1:
+            raise ValueError('closest_backward: needs at least one face and one vertex')
+        pts = _f32(points.reshape(-1, 3), d)
+        q, bary = _f32(out['closest'], d), _f32(out['bary'], d)
+        face = out['face'].detach().to(device=d, dtype=torch.int32).contiguous()
+        g = None if g_d2 is None else _f32(g_d2.reshape(-1), d)
+        ga = None if g_attr is None else _f32(g_attr, d)
+        res = dotdict()
+        for k in want:
+            res[k] = torch.empty((n, 3) if k == 'dpts' else (int(n_verts), 3 if k == 'dverts' else Cn), dtype=torch.float32, device=d)
+        row = lambda t: _ptr(t) if t is not None and n else None
+        outs = (row(res.get('dpts')), _ptr(res.get('dverts')), _ptr(res.get('dattr')) if Cn else None)
+        if any(o is not None for o in outs):       # else: only empty arrays were asked for
+            check(self.lib.ra_mesh_closest_backward(self.ctx, _ptr(faces), faces.shape[0], int(n_verts), row(pts), row(q), row(face), row(bary), n,
+                                                    row(g), row(ga) if Cn else None, Cn, *outs, self.stream), 'ra_mesh_closest_backward')
+        return res
 
     def topology(self, faces, n_verts):
         """faces (F,3) integer, n_verts -> a Topology handle (include/relightableavatar.h: ra_topo_create).  Faces on the device make

@@ -27,6 +27,9 @@
     icp_loss(v, t, n0, n1, dist_th, angle_th)                         :265-291 (Mesh.icp_residual: ra_icp_residual)
     bidirectional_icp_fitting(v0, f0, v1, f1, ...)                    :294-379 (relightableavatar_amd.largesteps)
     isosurface_fitting(src_verts, src_faces, tar_verts, tar_faces, ...)   :1018-1058 (Mesh.winding_grad: ra_mesh_winding_grad)
+    point_mesh_distance(points, verts, faces)                         lib/utils/sample_utils.py:198-307 (PointMeshDistance; Mesh.closest_backward)
+    point_to_surface_loss / chamfer_loss                              the mesh evaluator's two metrics as differentiable losses
+    point_cloud_fitting(src_verts, src_faces, tar_pts, ...)           isosurface_fitting's mould on a raw point cloud (ra_mesh_closest_backward)
     marching_cubes(volume, iso, attrs=None)                           an autograd op in volume and attrs (ra_marching_cubes_backward, _attrs)
     differentiable_marching_cubes(points, decoder, chunk_size, gradient=)   :70-127 (RegisterSDFGradient: 'normal'; the exact one: 'grid')
 
@@ -34,11 +37,18 @@ The distance and winding functions take the engine that owns the HIP context (en
 have no CPU fallback.  sample_blend_K_closest_points, sample_closest_points, the grid helpers, sample_surface and load_obj are plain torch / text and run anywhere.  Batches: the reference's signatures carry a
 batch dimension; B == 1 is supported, B > 1 is refused.
 
-Autograd.  winding_number, winding_number_nooom, bvh_distance and winding_distance are differentiable in pts, never in the mesh.  With
-pts.requires_grad the winding number comes from Mesh.winding_grad — the same bits, with the gradient of the computed function in
-closed form — and the distance's gradient is (p - closest) / d with the closest point held constant, which
-is also its true derivative (0 where d == 0).  Without it the calls made and the bits returned are those of the plain queries.
-mesh=: an engine Mesh already built of (verts, faces) serves the call and stays open; verts and faces are then not read.
+Autograd.  winding_number and winding_number_nooom are differentiable in pts, never in the mesh: with pts.requires_grad the winding
+number comes from Mesh.winding_grad — the same bits, with the gradient of the computed function in closed form.
+The distances — bvh_distance, winding_distance (through its distance factor), point_mesh_distance, sample_closest_points_on_surface,
+point_to_surface_loss, chamfer_loss — are differentiable in pts AND in verts, and the interpolated values in `values`.  In pts alone the
+gradient is (p - closest) / d with the closest point held constant, which is also the true derivative (0 where d == 0).  With
+verts.requires_grad (or values.requires_grad) the backward is Mesh.closest_backward (ra_mesh_closest_backward): for
+the face and barycentrics the query returned, d(d2)/dp = 2 (p - closest) and d(d2)/dv_k = -2 b_k (p - closest), and values receive
+b_k x the upstream gradient; sorted run sums, no float atomics, the same bits on every run.  The gradients THROUGH the closest point and
+the barycentrics themselves (second order for the distance) are not taken.  Without requires_grad on verts / values the calls made and
+the bits returned are those of the plain queries (and of the pts-only backward).
+mesh=: an engine Mesh already built of (verts, faces) serves the call and stays open; faces is then not read, and verts only as the
+tensor the gradient goes to.
 
 The remesh keeps the reference's sequence (grid, vertex filter, surface filter, winding, shift x distance, -10 fill, marching cubes,
 largest component, scale) with Engine.marching_cubes and Engine.largest_component in the places of mcubes and trimesh.  Not kept, as in
@@ -97,7 +107,87 @@ class _MeshWinding(torch.autograd.Function):
         return (g[:, None] * grad).reshape(ctx.like[0]).to(device=ctx.like[1], dtype=ctx.like[2]), None
 
 
-def _mesh_distance(mesh, pts):
+class _MeshClosestGrad(torch.autograd.Function):
+    """Mesh.closest forwards — d2, the face, and with values the values interpolated at the closest point —, Mesh.closest_backward
+    backwards: to pts, to verts, and to values (in groups of 64 channels).  The face and the barycentrics are constants of the backward."""
+
+    @staticmethod
+    def forward(ctx, pts, verts, values, mesh):
+        p = pts.detach().reshape(-1, 3)
+        out = mesh.closest(p, want=('d2', 'closest', 'face', 'bary'))
+        interp = None
+        if values is not None:
+            vals = values.detach().reshape(-1, values.shape[-1]).to(out.bary.device)
+            corners = mesh.faces_device().long()[out.face.long().clamp_min(0)]       # (N,3); face -1 (a non-finite point) has NaN barycentrics
+            interp = (vals[corners] * out.bary[..., None].to(vals.dtype)).sum(1)
+        ctx.eng, ctx.faces, ctx.n_verts = mesh._live_engine(), mesh.faces_device(), mesh.n_verts
+        ctx.save_for_backward(p, out.closest, out.face, out.bary)
+        ctx.like = [None if t is None else (t.shape, t.device, t.dtype) for t in (pts, verts, values)]
+        face = out.face.long()
+        ctx.mark_non_differentiable(face)
+        return out.d2, face, interp
+
+    @staticmethod
+    def backward(ctx, g_d2, _g_face, g_interp=None):
+        p, closest, face, bary = ctx.saved_tensors
+        out = dict(closest=closest, face=face, bary=bary)
+        need_p, need_v, need_a = ctx.needs_input_grad[:3]
+        back = lambda t, like: t.reshape(like[0]).to(device=like[1], dtype=like[2])
+        dp = dv = da = None
+        want = tuple(k for k, need in zip(('dpts', 'dverts'), (need_p, need_v)) if need)
+        if want:
+            res = ctx.eng.mesh_closest_backward(ctx.faces, ctx.n_verts, p, out, g_d2=g_d2, want=want)
+            dp = back(res.dpts, ctx.like[0]) if need_p else None
+            dv = back(res.dverts, ctx.like[1]) if need_v else None
+        if need_a and ctx.like[2] is not None:
+            g = g_interp.to(torch.float32)
+            parts = [ctx.eng.mesh_closest_backward(ctx.faces, ctx.n_verts, p, out, g_attr=g[:, c:c + 64].contiguous(), want=('dattr',)).dattr
+                     for c in range(0, g.shape[1], 64)]
+            da = back(torch.cat(parts, dim=1) if len(parts) != 1 else parts[0], ctx.like[2])
+        return dp, dv, da, None
+
+
+class _SafeSqrt(torch.autograd.Function):
+    """sqrt(d2) whose backward is g / (2 d), and 0 where d == 0: what _MeshDistance does for the distance in the points"""
+
+    @staticmethod
+    def forward(ctx, d2):
+        d = d2.sqrt()
+        ctx.save_for_backward(d)
+        return d
+
+    @staticmethod
+    def backward(ctx, g):
+        d, = ctx.saved_tensors
+        return torch.where(d > 0, g / (2 * d), torch.zeros_like(d))
+
+
+class _SurfacePoints(torch.autograd.Function):
+    """sum_k bary_k verts[faces[face][k]]: points that move with the mesh.  The backward is ra_mesh_closest_backward's attribute
+    path with the three coordinates as channels: the same sorted run sums, no float atomics."""
+
+    @staticmethod
+    def forward(ctx, verts, faces_dev, face, bary, eng):
+        v = verts.detach().to(eng.device, torch.float32)
+        ctx.eng, ctx.like = eng, (verts.shape, verts.device, verts.dtype)
+        ctx.save_for_backward(faces_dev, face, bary)
+        return (v[faces_dev.long()[face.long()]] * bary[..., None]).sum(1)
+
+    @staticmethod
+    def backward(ctx, g):
+        faces_dev, face, bary = ctx.saved_tensors
+        out = dict(closest=bary, face=face, bary=bary)           # closest and the points are not read on the attribute path
+        d = ctx.eng.mesh_closest_backward(faces_dev, ctx.like[0][0], bary, out, g_attr=g.contiguous(), want=('dattr',)).dattr
+        return d.reshape(ctx.like[0]).to(device=ctx.like[1], dtype=ctx.like[2]), None, None, None, None
+
+
+def _mesh_grad(t) -> bool:
+    return t is not None and torch.is_tensor(t) and _wants_grad(t)
+
+
+def _mesh_distance(mesh, pts, verts=None):
+    if _mesh_grad(verts):
+        return _SafeSqrt.apply(_MeshClosestGrad.apply(pts, verts, None, mesh)[0])
     return _MeshDistance.apply(pts, mesh) if _wants_grad(pts) else mesh.closest(pts, want=('d2',)).d2.sqrt()
 
 
@@ -107,17 +197,34 @@ def _mesh_winding(mesh, pts):
 
 def bvh_distance(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, engine=None, mesh=None) -> torch.Tensor:
     """pts (N,3), verts (V,3), faces (F,3) -> (N,) the plain (not squared) distance of every point to the mesh, |pts - closest| as the
-    reference computes it from bvh_distance_queries' closest points.  Differentiable in pts."""
+    reference computes it from bvh_distance_queries' closest points.  Differentiable in pts and in verts (see the module's Autograd)."""
     if pts.ndim != 2 or (mesh is None and (verts.ndim != 2 or faces.ndim != 2)):
         raise ValueError('bvh_distance: pts (N,3), verts (V,3), faces (F,3) — the reference adds the batch dimension itself')
     own = mesh is None
     if own:
         mesh = _engine(engine).mesh(verts, faces)
     try:
-        return _mesh_distance(mesh, pts)
+        return _mesh_distance(mesh, pts, verts)
     finally:
         if own:
             mesh.close()
+
+
+def point_mesh_distance(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, engine=None):
+    """lib/utils/sample_utils.py:198-307 (PointMeshDistance): points (N,3), verts (V,3), faces (F,3) -> (dists (N,) the plain distance
+    of every point to the mesh, face_idx (N,) int64 the face that attains it; -1 for a non-finite point).  Differentiable in points
+    and in verts: the upstream gradient g of the distance enters ra_mesh_closest_backward as g / (2 d) on d2, 0 where d == 0."""
+    if points.ndim != 2 or verts.ndim != 2 or faces.ndim != 2:
+        raise ValueError('point_mesh_distance: points (N,3), verts (V,3), faces (F,3); batches are not supported')
+    mesh = _engine(engine).mesh(verts, faces)
+    try:
+        if _wants_grad(points) or _wants_grad(verts):
+            d2, face, _ = _MeshClosestGrad.apply(points, verts, None, mesh)
+            return _SafeSqrt.apply(d2), face
+        out = mesh.closest(points, want=('d2', 'face'))
+        return out.d2.sqrt(), out.face.long()
+    finally:
+        mesh.close()
 
 
 def sample_closest_points_on_surface(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, values: torch.Tensor = None, engine=None):
@@ -128,7 +235,9 @@ def sample_closest_points_on_surface(points: torch.Tensor, verts: torch.Tensor, 
     square root of pytorch3d's squared point-to-face distance.
     The values are interpolated with the barycentrics of the CLOSEST POINT in its face.  The reference takes those of the query point's
     projection onto the face's plane (points_to_barycentric, :432-445), which may lie outside the face and then extrapolates; the two
-    agree wherever the closest point is interior to the face."""
+    agree wherever the closest point is interior to the face.
+    Differentiable in verts (the distance) and in values (the interpolated values: b_k x the upstream gradient, through
+    ra_mesh_closest_backward's attribute path) when they require a gradient; the barycentrics are constants of the backward."""
     if points.ndim != 3 or verts.ndim != 3 or faces.ndim != 3:
         raise ValueError('sample_closest_points_on_surface: points (B,N,3), verts (B,V,3), faces (B,F,3)')
     if points.shape[0] != 1 or verts.shape[0] != 1 or faces.shape[0] != 1:
@@ -136,6 +245,11 @@ def sample_closest_points_on_surface(points: torch.Tensor, verts: torch.Tensor, 
     n = points.shape[1]
     mesh = _engine(engine).mesh(verts[0], faces[0])
     try:
+        if _mesh_grad(verts) or _mesh_grad(values):
+            d2, _, interp = _MeshClosestGrad.apply(points, verts, values, mesh)
+            # pts alone keeps today's backward below; here d2's gradient reaches points and verts through the same call
+            d = _SafeSqrt.apply(d2).view(1, n, 1)
+            return d if values is None else (interp.view(1, n, -1), d)
         if values is None:
             return mesh.closest(points[0], want=('d2',)).d2.sqrt().view(1, n, 1)
         out = mesh.closest(points[0], want=('d2', 'face', 'bary'))
@@ -394,7 +508,8 @@ def winding_shift(winding: torch.Tensor, level_set: float = 0.5, winding_th: flo
 def winding_distance(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, winding_th: float = 0.45, engine=None, mesh=None) -> torch.Tensor:
     """pts (N,3) -> (N,) the signed distance to the mesh, positive INSIDE: the closest-point distance times the clamped winding sign.
     One mesh is built and serves both queries.  Differentiable in pts: 2 d grad(w) where the shift is neither clipped nor snapped
-    (exactly 0 elsewhere), plus shift grad(d)."""
+    (exactly 0 elsewhere), plus shift grad(d).  Differentiable in verts through the distance factor alone (shift x d d / d verts): the
+    winding number has no gradient in the mesh."""
     own = mesh is None
     if own:
         _check_mesh_args('winding_distance', pts, verts, faces)
@@ -402,7 +517,7 @@ def winding_distance(pts: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor
     elif pts.ndim != 2:
         raise ValueError('winding_distance: pts (N,3); batches are not supported')
     try:
-        d = _mesh_distance(mesh, pts)
+        d = _mesh_distance(mesh, pts, verts)
         return winding_shift(_mesh_winding(mesh, pts), 0.5, winding_th) * d
     finally:
         if own:
@@ -719,6 +834,95 @@ def isosurface_fitting(src_verts: torch.Tensor, src_faces: torch.Tensor, tar_ver
             optim.step()
     finally:
         target.close()
+    return M.solve(param.detach(), x0=verts)
+
+
+def _distance_mean(mesh, pts, verts, squared=False):
+    """mesh_evaluator.mean_distance's arithmetic — sqrt(d2) in double, then the mean — as a differentiable 0-d float64 tensor"""
+    if _mesh_grad(verts):
+        d2 = _MeshClosestGrad.apply(pts, verts, None, mesh)[0].double()
+    elif _wants_grad(pts):
+        d2 = _MeshClosestGrad.apply(pts, None, None, mesh)[0].double()
+    else:
+        d2 = mesh.closest(pts, want=('d2',)).d2.double()
+    return (d2 if squared else _SafeSqrt.apply(d2)).mean()
+
+
+def point_to_surface_loss(verts: torch.Tensor, faces: torch.Tensor, points: torch.Tensor, squared: bool = False, engine=None) -> torch.Tensor:
+    """the mean distance (squared: the mean squared distance) of points (N,3) to the mesh (verts (V,3), faces (F,3)): the mesh
+    evaluator's point-to-surface metric (mesh_evaluator.mean_distance) as a loss, a 0-d float64 tensor on the device.  Differentiable
+    in verts — the points of a fixed scan pull the moving mesh — and in points."""
+    _check_mesh_args('point_to_surface_loss', points, verts, faces)
+    mesh = _engine(engine).mesh(verts, faces)
+    try:
+        return _distance_mean(mesh, points, verts, squared)
+    finally:
+        mesh.close()
+
+
+def chamfer_loss(verts: torch.Tensor, faces: torch.Tensor, tgt_verts: torch.Tensor, tgt_faces: torch.Tensor, src_pts_bary, tgt_pts: torch.Tensor,
+                 engine=None) -> torch.Tensor:
+    """mesh_evaluator.chamfer_and_p2s's Chamfer distance as a loss, differentiable in verts (V,3): (mean distance of the source samples
+    to the target mesh + mean distance of tgt_pts (M,3) to the source mesh) / 2, a 0-d float64 tensor on the device.  src_pts_bary =
+    (face (N,) integer, bary (N,3)): the source samples as faces and barycentrics of the source mesh, so that they move with it (from
+    sample_surface: the face ids it returns, and the barycentrics of its points).  The first half reaches verts through the samples,
+    the second through ra_mesh_closest_backward; neither uses float atomics."""
+    _check_mesh_args('chamfer_loss', tgt_pts, verts, faces)
+    eng = _engine(engine)
+    dev = eng.device
+    face, bary = src_pts_bary
+    faces_dev = faces.detach().to(dev, torch.int32).reshape(-1, 3).contiguous()
+    face, bary = face.detach().to(dev, torch.int32).contiguous(), bary.detach().to(dev, torch.float32).contiguous()
+    if face.ndim != 1 or tuple(bary.shape) != (face.shape[0], 3):
+        raise ValueError('chamfer_loss: src_pts_bary = (face (N,), bary (N,3))')
+    src_pts = _SurfacePoints.apply(verts, faces_dev, face, bary, eng) if _wants_grad(verts) else \
+        (verts.detach().to(dev, torch.float32)[faces_dev.long()[face.long()]] * bary[..., None]).sum(1)
+    tgt = eng.mesh(tgt_verts.detach(), tgt_faces)
+    try:
+        src_tgt = _distance_mean(tgt, src_pts, None)
+    finally:
+        tgt.close()
+    src = eng.mesh(verts, faces)
+    try:
+        tgt_src = _distance_mean(src, tgt_pts, verts)
+    finally:
+        src.close()
+    return (src_tgt + tgt_src) / 2
+
+
+def point_cloud_fitting(src_verts: torch.Tensor, src_faces: torch.Tensor, tar_pts: torch.Tensor, param_lambda: int = 29, opt_iter: int = 100,
+                        chunk_size: int = None, lr: float = 1e-3, generator: torch.Generator = None, engine=None):
+    """Fit a mesh to a raw point cloud (no faces), in the mould of isosurface_fitting: the source is parameterised by u = (I +
+    param_lambda L) v (relightableavatar_amd.largesteps) and optimised with AdamUniform on the mean squared distance of tar_pts (N,3) —
+    or, with chunk_size, of chunk_size of them drawn per iteration by torch.randperm with `generator` (on the generator's device; the
+    engine's without one) — to the MOVING mesh: the scan-to-mesh half of Chamfer, whose gradient in the vertices is
+    ra_mesh_closest_backward's.  Per iteration the solve is warm-started from the previous vertices and the mesh is rebuilt from the
+    moved ones (its faces stay on the device); nothing is read back.  Returns the float32 vertices (V,3) on the device."""
+    from . import largesteps
+    eng = _engine(engine)
+    dev = eng.device
+    verts = src_verts.detach().to(dev, torch.float32).contiguous()
+    if verts.ndim != 2 or verts.shape[-1] != 3 or tar_pts.ndim != 2 or tar_pts.shape[-1] != 3:
+        raise ValueError('point_cloud_fitting: src_verts (V,3), tar_pts (N,3); batches are not supported')
+    faces_host = src_faces.detach().to('cpu', torch.int32).reshape(-1, 3).contiguous()
+    faces_dev = faces_host.to(dev)
+    target = tar_pts.detach().to(dev, torch.float32).contiguous()
+    M = largesteps.compute_matrix(verts, faces_host, param_lambda, engine=eng)
+    param = largesteps.to_differential(M, verts).detach().requires_grad_()
+    optim = largesteps.AdamUniform([param], lr=lr, engine=eng)
+    perm_dev = dev if generator is None else generator.device
+    for _ in range(int(opt_iter)):
+        w = largesteps.from_differential(M, param, 'Cholesky', x0=verts)
+        verts = w.detach()
+        query = target if chunk_size is None else target[torch.randperm(len(target), device=perm_dev, generator=generator)[:chunk_size].to(dev)]
+        mesh = eng.mesh(verts, faces_host, faces_dev=faces_dev)
+        try:
+            loss = _MeshClosestGrad.apply(query, w, None, mesh)[0].mean()
+            optim.zero_grad(set_to_none=True)
+            loss.backward()
+            optim.step()
+        finally:
+            mesh.close()
     return M.solve(param.detach(), x0=verts)
 
 
