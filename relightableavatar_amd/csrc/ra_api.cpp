@@ -1,6 +1,6 @@
 // C ABI: orchestration of the render hot path (include/relightableavatar.h) — the distance and full queries, the sphere trace, the
 // light-visibility stage and the three render chunks.  The context itself is ra_api_ctx.cpp, the thin entry points ra_api_ops.cpp,
-// the test hooks ra_api_debug.cpp.
+// the mesh-side domains ra_api_mesh, _topo, _cloth, _raster and _mcubes.cpp, the test hooks ra_api_debug.cpp.
 // Every entry point only enqueues work on the caller's stream; counts that steer later passes
 // (fine points, hit pixels, shadow rays) stay on the device and kernels size themselves from them.
 #include "ra_api_impl.hpp"

@@ -1,6 +1,6 @@
-// What the ra_api*.cpp files share: the argument-check macro, the chunk counters and those hot-path passes of ra_api.cpp that the
-// thin entry points (ra_api_ops.cpp) and the test hooks (ra_api_debug.cpp) call; hdq_pass, fine_level and forward_pass have no caller
-// outside ra_api.cpp and stay private to it.
+// What the ra_api*.cpp files share: the argument-check macro, the lifecycle of the handles a context owns, the chunk counters and those
+// hot-path passes of ra_api.cpp that the thin entry points (ra_api_ops.cpp, ra_api_mcubes.cpp) and the test hooks (ra_api_debug.cpp)
+// call; hdq_pass, fine_level and forward_pass have no caller outside ra_api.cpp and stay private to it.
 #pragma once
 #include "ra_ctx.hpp"
 
@@ -11,6 +11,18 @@
             return 1;                \
         }                            \
     } while (0)
+
+// the handles of a context (ra_ctx::meshes, topos, cloths): p if v owns it, else null
+template <typename T> static T* owned(const std::vector<std::unique_ptr<T>>& v, const T* p) {
+    for (auto& u : v) if (u.get() == p) return u.get();
+    return nullptr;
+}
+// ... and its end: the device current and idle first (launches that read the handle may still be queued), then out of v
+template <typename T> static void release_owned(ra_ctx* c, std::vector<std::unique_ptr<T>>& v, const T* p) {
+    hipSetDevice(c->device);
+    hipDeviceSynchronize();
+    for (auto it = v.begin(); it != v.end(); ++it) if (it->get() == p) { v.erase(it); break; }
+}
 
 // weights finalized, a frame set, the context's device current; who: the entry point, for the message
 int check_ready(ra_ctx* c, const char* who);

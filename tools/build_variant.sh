@@ -12,7 +12,7 @@ nos=-fno-slp-vectorize; case $base in ra_k3cc_*) nos="-fno-slp-vectorize -mllvm 
 ext=hip; xf=""; [ -f $C/$base.cpp ] && { ext=cpp; xf="-x hip"; }
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-value $nos $flags $xf -c $C/$base.$ext -o $R/gpurun_tmp/variants/$name.o
 objs=""
-for o in ra_k3_f16 ra_k3_bf16 ra_k3c_f16 ra_k3cc_f16 $EXTRA_OBJ ra_k4_fwd_f16 ra_k4_bwd_f16 ra_k4_fwd_bf16 ra_k4_bwd_bf16 ra_k4_canon_f16 ra_k4_canon_bf16 ra_hdq ra_trace ra_shade_bwd ra_heads ra_entropy ra_metrics ra_lpips ra_image ra_api ra_api_ctx ra_api_ops ra_api_debug ra_pack ra_shard; do
+for o in $(make -s -C $C print-objs | sed 's/\.o\b//g') $EXTRA_OBJ; do      # the product's objects (csrc/Makefile OBJS), then the caller's own
   ov=""; for kv in $OVERRIDE; do [ "${kv%%=*}" = $o ] && ov="${kv#*=}"; done       # OVERRIDE="ra_k3_f16=path.o ...": further objects to swap
   if [ $o = $base ]; then objs="$objs $R/gpurun_tmp/variants/$name.o"; elif [ -n "$ov" ]; then objs="$objs $ov"; else objs="$objs $C/$o.o"; fi
 done
